@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """sfmx bench — descriptor-pairs/s matched + ms per LM iteration (BASELINE.json metric).
 
-One JSON line.  Top level: the SIFT leg on BASELINE config 2; nested "orb": the
-ORB leg on config 4; nested "c3": 200 x 8192 SIFT unordered (config 3, 19900
-pairs sharded over the N ranks); nested "ba": the bundle-adjustment leg on
-config 5.
+One JSON line.  Top level: the SIFT leg on BASELINE config 2.  A plain run
+(`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps of that
+leg, writes its outputs if `--dump-outputs DIR` is given and prints the line.
+`--full` adds everything else: nested "orb": the ORB leg on config 4; nested
+"c3": 200 x 8192 SIFT unordered (config 3, 19900 pairs sharded over the N
+ranks); nested "ba": the bundle-adjustment leg on config 5; the homography,
+3D-2D, MVS and extraction legs; the CPU baselines and parity checks against
+the oracle; the PCIe-inclusive call; the detail side file.
 
 Matching step = one pass of the hot path over the whole synthetic job with the
 descriptors already resident in HBM: prepare every image (f32 -> int8 + norms,
@@ -13,7 +17,8 @@ this rank's shard, slow-path check, match-graph assembly (counts, filters,
 packed DMatch lists in HBM).  The D2H of the match lists is not in the timed
 region (`pcie_inclusive` reports the host-buffer rate separately).
 
-  python bench.py                          # N=1: SIFT 50 x 8192 (1225 pairs) + ORB 200 x 16384 grid + BA C5
+  python bench.py                          # N=1: SIFT 50 x 8192 (1225 pairs)
+  python bench.py --full                   # ... + ORB 200 x 16384 grid + BA C5 + the other legs + CPU baselines
   torchrun --nproc-per-node N bench.py --gpus N ...
 
 Multi-GPU, one process per GPU:
@@ -24,7 +29,7 @@ Multi-GPU, one process per GPU:
   C3:   strong scaling (the fixed 19900-pair 200-image job sharded across ranks).
   BA:   strong scaling (points sharded, S + rhs all-reduced over RCCL).
 Timing: barrier + synchronize on both sides, max over ranks.
-CPU baselines (rank 0, N=1 only): exact BF and FLANN-style restatements from
+CPU baselines (--full, rank 0, N=1 only): exact BF and FLANN-style restatements from
 oracle/ on a bounded prefix of the same pairs; `cpu_baseline` is the faster.
 """
 from __future__ import annotations
@@ -65,8 +70,15 @@ def parse(argv=None):
     ap.add_argument("--launch-probe", action="store_true",
                     help="launcher test only: each rank joins a gloo group, all-reduces its rank and exits "
                          "(no GPU, no torch.cuda call)")
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps of the headline leg")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the ORB / C3 / BA / homography / 3D-2D / MVS / "
+                         "extraction legs, the CPU baselines and parity checks against the oracle, the PCIe-inclusive "
+                         "call and the detail side file (each still switched off by its --no-* flag); needed by --only-*")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step of the headline leg computed (the arrays "
+                         "BFMatcher.fetch returns) as DIR/<name>.npy")
     ap.add_argument("--workload", choices=["sift", "orb"], default="sift")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="target length of each CPU-baseline sample")
@@ -88,7 +100,13 @@ def parse(argv=None):
     ap.add_argument("--ba-cpu-iters", type=int, default=2, help="LM iterations of the CPU BA baseline sample")
     ap.add_argument("--no-ba-weak", action="store_true",
                     help="N > 1: skip the BA weak-scaling problem (200 cams x 200k*N points)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    only = [f for f in ("only_orb_features", "only_features", "only_ba", "only_c3") if getattr(args, f)]
+    if only and not args.full:
+        ap.error(f"--{only[0].replace('_', '-')} selects a leg of the full run: add --full")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def resolve_world(args, env=None):
@@ -255,31 +273,33 @@ def main():
             import traceback
             traceback.print_exc()
             return {"error": f"{type(e).__name__}: {e}"[:300]}
-    orb = c3 = None
-    if args.workload == "sift" and not args.no_orb:
-        orb = leg(bench_match, "orb", args, rank, world, local)
-    if args.workload == "sift" and not args.no_c3:
-        c3 = leg(bench_match, "c3", args, rank, world, local)
-    ba_res = None if args.no_ba else leg(bench_ba, args, rank, world, local)
-    if ba_res is not None and "error" not in ba_res and world == 1 and not args.no_ba_calls:
-        ba_res["calls"] = leg(bench_ba_calls, args)
-    mvs_res = None if args.no_mvs else leg(bench_mvs, args, rank, world, local)
-    feat_res = None if args.no_features else leg(bench_features, args, rank, world, local)
-    orbf_res = None if args.no_orb_features else leg(bench_features_orb, args, rank, world, local)
+    orb = c3 = ba_res = mvs_res = feat_res = orbf_res = None
+    if args.full:   # a plain run ends with the headline leg
+        if args.workload == "sift" and not args.no_orb:
+            orb = leg(bench_match, "orb", args, rank, world, local)
+        if args.workload == "sift" and not args.no_c3:
+            c3 = leg(bench_match, "c3", args, rank, world, local)
+        ba_res = None if args.no_ba else leg(bench_ba, args, rank, world, local)
+        if ba_res is not None and "error" not in ba_res and world == 1 and not args.no_ba_calls:
+            ba_res["calls"] = leg(bench_ba_calls, args)
+        mvs_res = None if args.no_mvs else leg(bench_mvs, args, rank, world, local)
+        feat_res = None if args.no_features else leg(bench_features, args, rank, world, local)
+        orbf_res = None if args.no_orb_features else leg(bench_features_orb, args, rank, world, local)
     if rank == 0:
         full = {k: v for k, v in primary.items() if not k.startswith("_")}
         if orb is not None:
             full["orb"] = {k: v for k, v in orb.items() if not k.startswith("_")}
         if c3 is not None:
             full["c3"] = {k: v for k, v in c3.items() if not k.startswith("_")}
-        full["ba"] = ba_res
+        if args.full:
+            full["ba"] = ba_res
         if mvs_res is not None:
             full["mvs"] = mvs_res
         if feat_res is not None:
             full["features"] = feat_res
         if orbf_res is not None:
             full["features_orb"] = orbf_res
-        detail = write_detail(full)
+        detail = write_detail(full) if args.full else None
         print(json.dumps(compact_line(full, detail)), flush=True)
     if world > 1:
         dist.barrier()
@@ -507,36 +527,44 @@ def bench_match(kind, args, rank, world, local):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # sanity outside the timed region
-    got, off, _ = matcher.fetch(stream=stream)
-    homog = f4 = None
-    if kind == "sift" and not args.no_homography:
-        homog = bench_homography(args, matcher, imgs, my_pairs, got, off, rank, world, local, stream)
-    if kind == "sift" and not args.no_f4:
-        f4 = bench_3d2d(args, imgs, my_pairs, got, off, rank, world, local, stream)
-    slow, f32p = matcher.stats(stream=stream)
-    n_matches = int(off[-1])
-    if world > 1:
-        t = torch.tensor([n_matches], dtype=torch.int64, device=f"cuda:{local}")
-        dist.all_reduce(t)
-        n_matches = int(t.item())
+    # outside the timed region: the last timed step's results, read for --dump-outputs and for --full's checks
+    dump = args.dump_outputs if kind == args.workload else None
+    homog = f4 = slow = f32p = n_matches = None
+    if dump or args.full:
+        got, off, keep = matcher.fetch(stream=stream)
+    if dump:
+        dump_outputs(dump, rank, {"matches": got, "pair_offsets": off, "keep": keep[:len(my_pairs)]})
+    if args.full:
+        if kind == "sift" and not args.no_homography:
+            homog = bench_homography(args, matcher, imgs, my_pairs, got, off, rank, world, local, stream)
+        if kind == "sift" and not args.no_f4:
+            f4 = bench_3d2d(args, imgs, my_pairs, got, off, rank, world, local, stream)
+        slow, f32p = matcher.stats(stream=stream)
+        n_matches = int(off[-1])
+        if world > 1:
+            t = torch.tensor([n_matches], dtype=torch.int64, device=f"cuda:{local}")
+            dist.all_reduce(t)
+            n_matches = int(t.item())
 
     value = logical_total * steps / elapsed   # all ranks' pairs / max-over-ranks time
     kern_ms = float(np.median(main_ms))
 
     # PCIe-inclusive rate (outside the timed region; never `value`): host descriptor
     # buffers in, H2D + prepare + match + D2H of the DMatch lists, as the one-shot ABI sees it.
-    barrier()
-    tp = time.perf_counter()
-    matcher.set_images(imgs, stream=stream)
-    matcher.run(my_pairs, sfmx.LOWE_RATIO, stream=stream)
-    matcher.fetch(stream=stream)
-    barrier()
-    pcie_s = time.perf_counter() - tp
-    if world > 1:
-        t = torch.tensor([pcie_s], dtype=torch.float64, device=f"cuda:{local}")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        pcie_s = float(t.item())
+    # A call of its own, so --full only.
+    pcie_s = None
+    if args.full:
+        barrier()
+        tp = time.perf_counter()
+        matcher.set_images(imgs, stream=stream)
+        matcher.run(my_pairs, sfmx.LOWE_RATIO, stream=stream)
+        matcher.fetch(stream=stream)
+        barrier()
+        pcie_s = time.perf_counter() - tp
+        if world > 1:
+            t = torch.tensor([pcie_s], dtype=torch.float64, device=f"cuda:{local}")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            pcie_s = float(t.item())
     matcher.close()
     achieved = logical_mine * op_per_pair / (kern_ms * 1e-3) / 1e12
     screen_ms = float(np.median(scr_ms))
@@ -567,7 +595,8 @@ def bench_match(kind, args, rank, world, local):
                      "screen_only": screen,
                      "algorithmic": f"{algo} x {logical_mine:.4g} pairs per launch"},
         "cpu_baseline": None,
-        "pcie_inclusive": {"value": logical_total / pcie_s, "unit": "descriptor-pairs/s", "ms": pcie_s * 1e3,
+        "pcie_inclusive": None if pcie_s is None else
+                          {"value": logical_total / pcie_s, "unit": "descriptor-pairs/s", "ms": pcie_s * 1e3,
                            "what": "host descriptors -> H2D + prepare + match + D2H of all DMatch lists, one call"},
         "matches": n_matches,
         "slow_path_queries": slow,
@@ -586,12 +615,35 @@ def bench_match(kind, args, rank, world, local):
         res["homography"] = homog
     if f4 is not None:
         res["find_3d2d"] = f4
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res.update(cpu_baselines("sift" if kind == "c3" else kind, imgs, pairs_all, got, off,
                                  args.cpu_seconds if kind != "c3" else min(args.cpu_seconds, 6.0)))
     del dev_imgs
     torch.cuda.empty_cache()
     return res
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, rank, arrays):
+    """--dump-outputs: each array as <name>.npy (rank r > 0: <name>.rank<r>.npy) in float64, which holds
+    every int32 index, float32 distance and offset below 2^53 exactly.  A record array becomes one
+    column per field.  If the arrays together pass DUMP_MAX_BYTES, each keeps a fixed seeded sample
+    of its rows (sorted, the same rows for the same shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    cols = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.names:
+            a = np.stack([a[f].astype(np.float64) for f in a.dtype.names], axis=1)
+        cols[name] = np.ascontiguousarray(a, np.float64)
+    total = sum(a.nbytes for a in cols.values())
+    for name, a in cols.items():
+        if total > DUMP_MAX_BYTES:
+            n = max(1, int(len(a) * DUMP_MAX_BYTES / total))
+            a = a[np.sort(np.random.default_rng(0x5F3D).choice(len(a), n, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
 
 
 def bench_homography(args, matcher, imgs, my_pairs, got, off, rank, world, local, stream):

@@ -5,6 +5,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,6 +86,49 @@ def test_failed_legs_leave_an_error_not_a_missing_line():
     assert len(line["legs"]["mvs"]["error"]) <= 300
     assert "ba_calls" not in line["legs"]
     assert len(json.dumps(line)) <= bench.LINE_MAX_BYTES and line["roofline"]["frac"] is not None
+
+
+def test_plain_run_options():
+    """A plain run measures the headline leg alone; the other legs, the CPU baselines and the
+    single-leg selectors sit behind --full."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 3)
+    a = bench.parse(["--full", "--only-ba", "--dump-outputs", "d"])
+    assert a.full and a.only_ba and a.dump_outputs == "d"
+    for only in ("--only-ba", "--only-c3", "--only-features", "--only-orb-features"):
+        with pytest.raises(SystemExit):
+            bench.parse([only])
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_plain_run_line_keeps_the_headline():
+    full = _full()
+    plain = {k: v for k, v in full.items() if k in HEAD and k != "cpu_baseline"}
+    line = bench.compact_line(plain, None)
+    assert list(line)[:len(HEAD)] == HEAD
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps"):
+        assert line[k] == pytest.approx(full[k], rel=1e-5) if isinstance(full[k], float) else line[k] == full[k]
+    assert line["legs"] == {} and line["detail"] is None and line["cpu_baseline"] is None
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    m = np.zeros(5, [("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"), ("distance", "<f4")])
+    m["queryIdx"], m["trainIdx"], m["distance"] = np.arange(5), 2 ** 31 - 1 - np.arange(5), np.float32(1.1)
+    off = np.array([0, 2, 5, 2 ** 40], np.int64)
+    bench.dump_outputs(str(tmp_path / "a" / "b"), 0, {"matches": m, "pair_offsets": off})
+    got = np.load(tmp_path / "a" / "b" / "matches.npy")
+    assert got.dtype == np.float64 and got.shape == (5, 4)
+    assert np.array_equal(got[:, 1].astype(np.int64), m["trainIdx"]) and np.array_equal(got[:, 3].astype(np.float32), m["distance"])
+    assert np.array_equal(np.load(tmp_path / "a" / "b" / "pair_offsets.npy").astype(np.int64), off)
+    # over the size limit: the same sorted sample of rows every time, under the limit in total
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1024)
+    big = np.arange(1000, dtype=np.int64)
+    for d in ("c", "d"):
+        bench.dump_outputs(str(tmp_path / d), 1, {"x": big, "y": big[:100]})
+    x, y = np.load(tmp_path / "c" / "x.rank1.npy"), np.load(tmp_path / "c" / "y.rank1.npy")
+    assert x.nbytes + y.nbytes <= 1024 and len(x) > len(y) > 0 and np.all(np.diff(x) > 0)
+    assert np.array_equal(x, np.load(tmp_path / "d" / "x.rank1.npy"))
 
 
 def test_recorded_r06_line_kernel_time_within_the_step():

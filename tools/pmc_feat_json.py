@@ -1,6 +1,6 @@
 """HBM bytes per image of the extraction legs from tools/pmc_feat.sh: 2 x FETCH_SIZE + WRITE_SIZE
 (KiB counters; gfx950 FETCH_SIZE counts half of a wide streaming read, MI355X_MICROARCH.md) summed
-over every extraction dispatch of the profiled `bench.py --only-[orb-]features --steps 10` run,
+over every extraction dispatch of the profiled `bench.py --full --only-[orb-]features --steps 10` run,
 divided by the images it featurised (warm-up batch + 2 timed batches: 3 x 50 SIFT, 3 x 200 ORB).
 python tools/pmc_feat_json.py DIR OUT.json (tooling)"""
 import collections, csv, glob, json, sys

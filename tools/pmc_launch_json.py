@@ -4,8 +4,8 @@ python tools/pmc_launch_json.py DIR N_LAUNCHES OUT.json   (tooling, not product)
 Since r04 a two-pass launch is several dispatches per kernel (the screen in batches on two streams,
 pass 2 per batch: matcher.cpp launch_two_pass_overlap), so a per-dispatch mean is no longer a
 per-launch figure.  Every counter is summed over all dispatches of a kernel in the profiled run and
-divided by the number of matcher launches in it (bench.py: warm-up + timed steps + the event steps
-+ the PCIe-inclusive call).  FETCH_SIZE / WRITE_SIZE stay in KiB (HBM read bytes = 2 x FETCH_SIZE on
+divided by the number of matcher launches in it (bench.py: warm-up + timed steps; with --full also
+the PCIe-inclusive call).  FETCH_SIZE / WRITE_SIZE stay in KiB (HBM read bytes = 2 x FETCH_SIZE on
 gfx950, MI355X_MICROARCH.md); bench.py's pmc_traffic reads this file's layout
 ({kernel: {counter: per-launch value}})."""
 import collections
