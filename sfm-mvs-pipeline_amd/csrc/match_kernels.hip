@@ -119,14 +119,17 @@ __global__ void prep_l2_kernel(const float* __restrict__ src, int rows, int cols
     prep_l2_row(src, r, rows, cols, dst, norm, keyc, keyc2, nonintegral);
 }
 // All images of a set_images call in one launch: blockIdx.y = image (table in HBM).
+constexpr int PREP_ROWS = 64;   // rows per workgroup of the batched prep
+static_assert(ROW_ALIGN % PREP_ROWS == 0 && PREP_ROWS % 8 == 0, "whole 8-row steps, no partial workgroup");
 __global__ void prep_l2_batch_kernel(const PrepImg* __restrict__ tab, int8_t* __restrict__ desc8,
                                      int32_t* __restrict__ norm, int32_t* __restrict__ keyc,
                                      int32_t* __restrict__ keyc2, int32_t* __restrict__ flags) {
     const PrepImg t = tab[blockIdx.y];
-    const int r = blockIdx.x * (blockDim.x >> 5) + (threadIdx.x >> 5);
-    if (r >= t.rows_pad) return;
-    prep_l2_row(t.src, r, t.rows, t.cols, desc8 + t.row0 * SIFT_DIM, norm + t.row0, keyc + t.row0, keyc2 + t.row0,
-                flags + blockIdx.y);
+    // PREP_ROWS rows per workgroup, 8 at a time (rows_pad is a multiple of PREP_ROWS)
+    for (int r = blockIdx.x * PREP_ROWS + (threadIdx.x >> 5); r < min((int)(blockIdx.x + 1) * PREP_ROWS, t.rows_pad);
+         r += blockDim.x >> 5)
+        prep_l2_row(t.src, r, t.rows, t.cols, desc8 + t.row0 * SIFT_DIM, norm + t.row0, keyc + t.row0, keyc2 + t.row0,
+                    flags + blockIdx.y);
 }
 __device__ __forceinline__ void prep_l2_row(const float* __restrict__ src, int r, int rows, int cols,
                                             int8_t* __restrict__ dst, int32_t* __restrict__ norm,
@@ -773,26 +776,55 @@ void sift_screen16_kernel(const WorkItem* __restrict__ work, const PairDev* __re
 // neighbour (sift_screen16_kernel), typically 2 of 16.  The workgroup gathers the pair's forwarded
 // queries with bit r, stages subset r's rows (j = r + 16 i, 256 per LDS chunk, the 8-bit local
 // index i & 255 in the packed key) and runs the exact top-2 of sift_knn2_kernel on them
-// (v_mfma_i32_32x32x32_i8, packed keys, 32 queries per wave).  Each (query, subset) top-2 is
-// merged into the query's global top-2 with two 64-bit atomicMin: key = (s << 32) | j, i.e.
-// (distance, train index) order; old = min(b0, k), then b1 = min(b1, max(old, k)) leaves b0 and
-// b1 the two smallest keys inserted, whatever the order (sift_settle_kernel reads them).
+// (v_mfma_i32_32x32x32_i8, packed keys, 32 queries per wave).
+//
+// The kernel is bound by its chain of memory round trips and by its atomics, not by its MFMAs.
+// Nothing in the staging depends on the query list, so chunk 0's LDS-DMA and the norms of its rows
+// are issued at entry: the gather and the query-row loads run under them, and the chunk's keys are
+// formed from norms that arrived with the rows (no second, dependent load).
+//
+// Merge: each (query, subset) top-2 k1 <= k2, key = (s << 32) | j, i.e. (distance, train index)
+// order, goes into the query's global pair (b0, b1), both ~0 before pass 2:
+//       old = atomicMin(b0, k1);  atomicMin(b1, max(old, k1));  atomicMin(b1, k2).
+// Invariant: b0 and b1 end as the two smallest keys inserted, in any arrival order.  b0 is the
+// minimum of every k1, hence of every key, since each k2 has its own k1 <= k2 below it.  The
+// atomics on b0 are serialised: every k1 but the smallest either finds b0 <= k1 and sends itself to
+// b1, or displaces an `old` that goes to b1, and the smallest k1 is never sent to b1 (it is never
+// displaced and displaces whatever it finds), so the k1 steps alone leave b1 = the second smallest
+// k1.  The second smallest key overall is the smaller of that and the smallest k2 (the k2 of
+// another insertion has its own k1 at or below it among the other k1), which is what reaches b1.
+// A k2 never needs the exchange on b0: k2 >= k1 >= b0 from the moment k1 is inserted, and the
+// minimum on b1 commutes with everything else, so it need not wait for k1's atomics either.
+// sift_settle_kernel reads (b0, b1).
+//
+// Most forwarded queries have exactly two flagged subsets.  Those need no atomics at all: the
+// lower subset's workgroup stores its (k1, k2) as one 16-B word over the query's pair in `top2`,
+// the upper one's into the same place of `slot1` (the matcher's packed output buffer, idle until
+// assembly), ~0 for a missing key, and sift_settle_kernel, which sees the same mask, merges the
+// two top-2.  Both workgroups exist and write: a mask of two bits comes from two subset maxima
+// that are real rows (r < nt), and the query is in its pair's list (cnt > 0).  The workgroup then
+// ends on plain stores instead of waiting for a returning atomic.  Every other mask (3+ subsets,
+// or all 16 when the screen's bound was not usable) takes the atomics above.
 template <int WAVES>
 __global__ __launch_bounds__(WAVES * 64, 2)
 void sift_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restrict__ imgs,
                         const int8_t* __restrict__ desc8, const int32_t* __restrict__ norm,
                         const int32_t* __restrict__ qlist, const int32_t* __restrict__ qmask,
                         const int32_t* __restrict__ qcount, const int32_t* __restrict__ porder,
-                        unsigned long long* __restrict__ top2) {
+                        unsigned long long* __restrict__ top2, unsigned long long* __restrict__ slot1) {
     constexpr int CH = 256;                   // rows per LDS chunk
     constexpr int QC = WAVES * 32;            // queries per tile group (one 32-query tile per wave)
     constexpr int WIN = 1024;                 // forwarded-query window scanned per round
     constexpr int GLDS = CH * SIFT_DIM / (WAVES * 64 * 16);
     static_assert(GLDS * WAVES * 64 * 16 == CH * SIFT_DIM, "chunk must split into whole 16-B pieces");
+    static_assert(WAVES * 64 == CH, "one thread per chunk row loads its norm");
     __shared__ __attribute__((aligned(16))) char rows_lds[CH * SIFT_DIM];
     __shared__ int keys_lds[CH];
     __shared__ int ql[WIN];
     __shared__ int s_n;
+    // four workgroups per CU (160 KB of LDS), as the 128-VGPR bound of four waves per SIMD allows
+    static_assert(sizeof(rows_lds) + sizeof(keys_lds) + sizeof(ql) + sizeof(s_n) <= 160 * 1024 / 4,
+                  "pass-2 LDS must leave four workgroups resident per CU");
 
     const int tid = threadIdx.x, wid = tid >> 6, lane = tid & 63, h = lane >> 5, l32 = lane & 31;
     const int item = xcd_remap(blockIdx.x, gridDim.x);
@@ -806,40 +838,61 @@ void sift_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restr
     const int32_t* qls = qlist + P.dense_base;
     const int32_t* qms = qmask + P.dense_base;
 
+    // Chunk c0's rows (XOR-swizzled 16-B pieces; rows past the subset's end are clamped to the
+    // chunk's first row, so every address lies in the image's padded rows) -> LDS by DMA;
+    // returns the norm of this thread's row of the chunk.
+    auto stage = [&](int c0, int rows) -> int {
+#pragma unroll
+        for (int u = 0; u < GLDS; ++u) {
+            const int p = u * WAVES * 64 + tid;
+            const int rr = p >> 3, slot = p & 7, c = slot ^ ((rr >> 1) & 7);
+            const int j = r + 16 * (c0 + (rr < rows ? rr : 0));
+            const int8_t* gp = desc8 + (R.row0 + j) * SIFT_DIM + 16 * c;
+            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gp,
+                                             (LDS_AS void*)(rows_lds + (u * WAVES + wid) * 1024), 16, 0, 0);
+        }
+        return norm[R.row0 + r + 16 * (c0 + (tid < rows ? tid : 0))];
+    };
+    int nv = stage(0, min(CH, nr));           // nr >= 32: r < nt
+    int cur = 0;                              // the chunk in (or on its way into) the LDS
+    bool fresh = true;                        // its keys are not written yet
+
     for (int e0 = 0; e0 < cnt; e0 += WIN) {
         if (tid == 0) s_n = 0;
         __syncthreads();
-        for (int e = e0 + tid; e < min(cnt, e0 + WIN); e += WAVES * 64)
-            if ((qms[e] >> r) & 1) ql[atomicAdd(&s_n, 1)] = qls[e];
+        for (int e = e0 + tid; e < min(cnt, e0 + WIN); e += WAVES * 64) {
+            const int mk = qms[e];
+            if ((mk >> r) & 1) {   // query row (< 2^18) | merge mode << 20: 0 atomics, 1 / 2 the lower / upper of two subsets
+                const int mode = __popc(mk) == 2 ? ((mk & ((1 << r) - 1)) ? 2 : 1) : 0;
+                ql[atomicAdd(&s_n, 1)] = qls[e] | (mode << 20);
+            }
+        }
         __syncthreads();
         const int n = s_n;
         for (int g0 = 0; g0 < n; g0 += QC) {
             const int qe = g0 + wid * 32 + l32;
-            const int qrow = qe < n ? ql[qe] : -1;
+            const int qpk = qe < n ? ql[qe] : -1;
+            const int qrow = qpk < 0 ? -1 : (qpk & 0xFFFFF), mode = qpk < 0 ? 0 : (qpk >> 20);
             const bool active = g0 + wid * 32 < n;   // wave-uniform
+            const int64_t lrow = L.row0 + (qrow < 0 ? 0 : qrow);
             i32x4 bq[4];
             {
-                const i32x4* src = reinterpret_cast<const i32x4*>(desc8 + (L.row0 + (qrow < 0 ? 0 : qrow)) * SIFT_DIM);
+                const i32x4* src = reinterpret_cast<const i32x4*>(desc8 + lrow * SIFT_DIM);
 #pragma unroll
                 for (int m = 0; m < 4; ++m) bq[m] = src[2 * m + h];
             }
+            const long long na = norm[lrow];
             int T1 = INT_MAX, J1 = -1, T2 = INT_MAX, J2 = -1;
             for (int c0 = 0; c0 < nr; c0 += CH) {
                 const int rows = min(CH, nr - c0);   // a multiple of 32
-                __syncthreads();                     // the previous chunk's readers are done
-#pragma unroll
-                for (int u = 0; u < GLDS; ++u) {
-                    const int p = u * WAVES * 64 + tid;
-                    const int rr = p >> 3, slot = p & 7, c = slot ^ ((rr >> 1) & 7);
-                    const int j = r + 16 * (c0 + (rr < rows ? rr : 0));
-                    const int8_t* gp = desc8 + (R.row0 + j) * SIFT_DIM + 16 * c;
-                    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gp,
-                                                     (LDS_AS void*)(rows_lds + (u * WAVES + wid) * 1024), 16, 0, 0);
+                if (cur != c0) {                     // (a one-chunk subset stays staged for every group)
+                    __syncthreads();                 // the previous chunk's readers are done
+                    nv = stage(c0, rows);
+                    cur = c0;
+                    fresh = true;
                 }
-                for (int i = tid; i < CH; i += WAVES * 64) {
-                    const int j = r + 16 * (c0 + i);
-                    keys_lds[i] = (i < rows && j < nt) ? (-(norm[R.row0 + j] << 8) + 255 - i) : INT_MIN;
-                }
+                if (fresh) keys_lds[tid] = (tid < rows && r + 16 * (c0 + tid) < nt) ? (-(nv << 8) + 255 - tid) : INT_MIN;
+                fresh = false;
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 if (active) {
@@ -883,21 +936,24 @@ void sift_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restr
                     }
                 }
             }
+            // (T1, J1) <= (T2, J2) in (distance, index) order: k1 <= k2 (see the merge above)
             if (active && h == 0 && qrow >= 0) {
-                const long long na = norm[L.row0 + qrow];
-                unsigned long long* b = top2 + 2 * (P.dense_base + qrow);
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int t_ = e == 0 ? T1 : T2, i_ = e == 0 ? J1 : J2;
-                    if (t_ == INT_MAX) continue;
-                    const unsigned long long k = ((unsigned long long)(na + t_) << 32) | (unsigned)(r + 16 * i_);
-                    const unsigned long long old = atomicMin(b, k);
-                    atomicMin(b + 1, old > k ? old : k);
+                const unsigned long long k1 = T1 != INT_MAX ? ((unsigned long long)(na + T1) << 32) | (unsigned)(r + 16 * J1) : ~0ull;
+                const unsigned long long k2 = T2 != INT_MAX ? ((unsigned long long)(na + T2) << 32) | (unsigned)(r + 16 * J2) : ~0ull;
+                if (mode != 0) {          // one of exactly two subsets: its own 16-B slot, no atomics
+                    unsigned long long* b = (mode == 1 ? top2 : slot1) + 2 * (P.dense_base + qrow);
+                    *reinterpret_cast<ulonglong2*>(b) = make_ulonglong2(k1, k2);
+                } else if (T1 != INT_MAX) {
+                    unsigned long long* b = top2 + 2 * (P.dense_base + qrow);
+                    if (T2 != INT_MAX) atomicMin(b + 1, k2);
+                    const unsigned long long old = atomicMin(b, k1);
+                    atomicMin(b + 1, old > k1 ? old : k1);
                 }
             }
         }
         __syncthreads();   // ql / s_n are rewritten by the next window
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // a staged chunk no group read: its LDS-DMA ends before the LDS is freed
 }
 
 // Pass 2, subset form: the forwarded queries' merged top-2 -> dense results (one workgroup per pair).
@@ -906,7 +962,8 @@ void sift_settle_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restr
                         const int32_t* __restrict__ qlist, const int32_t* __restrict__ qcount,
                         const unsigned long long* __restrict__ top2, int32_t* __restrict__ out_idx,
                         float* __restrict__ out_dist, int2* __restrict__ slow_list, int32_t* __restrict__ slow_count,
-                        double ratio, const int32_t* __restrict__ porder = nullptr) {
+                        double ratio, const int32_t* __restrict__ qmask, const unsigned long long* __restrict__ slot1,
+                        const int32_t* __restrict__ porder = nullptr) {
     const int pi = porder ? porder[blockIdx.x] : (int)blockIdx.x;   // porder: one batch's pairs (overlapped pass 2)
     const int cnt = qcount[pi];
     if (cnt == 0) return;
@@ -915,7 +972,13 @@ void sift_settle_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restr
     for (int e = threadIdx.x; e < cnt; e += 256) {
         const int qi = qlist[P.dense_base + e];
         const int64_t o = P.dense_base + qi;
-        const unsigned long long b0 = top2[2 * o], b1 = top2[2 * o + 1];
+        unsigned long long b0 = top2[2 * o], b1 = top2[2 * o + 1];
+        if (__popc(qmask[P.dense_base + e]) == 2) {   // two subsets, one slot each (sift_subset_kernel): merge the two top-2
+            const unsigned long long c0 = slot1[2 * o], c1 = slot1[2 * o + 1];
+            const unsigned long long lo = b0 < c0 ? b0 : c0, hi = b0 < c0 ? c0 : b0, m2 = b1 < c1 ? b1 : c1;
+            b0 = lo;
+            b1 = hi < m2 ? hi : m2;
+        }
         if (b0 == ~0ull || (nt >= 2 && b1 == ~0ull)) {
             if (nt == 0) { out_idx[o] = -1; out_dist[o] = 0.f; }   // an empty train image: no neighbour
             // otherwise pass 2 left a flagged subset unscanned: the UNSETTLED stamp stays, so
@@ -947,8 +1010,8 @@ __global__ void probe_xor80_kernel(uint32_t* __restrict__ p, int64_t n_words) {
 hipError_t launch_prep_l2_batch(const PrepImg* tab, int n, int max_rows_pad, int8_t* desc8, int32_t* norm,
                                 int32_t* keyc, int32_t* keyc2, int32_t* flags, hipStream_t st) {
     if (n == 0 || max_rows_pad == 0) return hipSuccess;
-    prep_l2_batch_kernel<<<dim3((unsigned)((max_rows_pad + 7) / 8), (unsigned)n), 256, 0, st>>>(tab, desc8, norm, keyc,
-                                                                                              keyc2, flags);
+    prep_l2_batch_kernel<<<dim3((unsigned)((max_rows_pad + PREP_ROWS - 1) / PREP_ROWS), (unsigned)n), 256, 0, st>>>(
+        tab, desc8, norm, keyc, keyc2, flags);
     return hipGetLastError();
 }
 // The per-image integrality flags into pinned, host-coherent memory, then a sequence word with
@@ -1855,27 +1918,6 @@ void orb_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restric
 // filter (trainIdx seen/dup bitsets in LDS, SfM.cpp:547-564), count, min_count
 // keep flag (SfM.cpp:566-570), then a second launch writes packed DMatch in
 // query order at the scanned pair offset.
-__device__ __forceinline__ int block_exclusive_scan(int v, int* sh, int& total) {
-    // 1024 threads = 16 waves
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
-    if (lane == 63) sh[wid] = x;
-    __syncthreads();
-    if (wid == 0) {
-        int s = lane < 16 ? sh[lane] : 0;
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) { const int y = __shfl_up(s, o); if (lane >= o) s += y; }
-        if (lane < 16) sh[16 + lane] = s;
-    }
-    __syncthreads();
-    const int wbase = wid ? sh[16 + wid - 1] : 0;
-    total = sh[31];
-    __syncthreads();
-    return wbase + x - v;
-}
-
 // mode 0: count -> counts[p], keep[p];  mode 1: write packed matches.
 template <int MODE>
 __global__ __launch_bounds__(1024)
@@ -1904,23 +1946,48 @@ void assemble_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restrict
         }
         __syncthreads();
     }
-    if (MODE == 0) {
-        int bad = 0;
-        for (int q = threadIdx.x; q < nq; q += blockDim.x) bad += ix[q] == UNSETTLED;
-        if (bad) atomicAdd(unsettled, bad);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;   // 1024 threads = 16 waves
+    if (MODE == 0) {   // one read of the pair's results: per-thread counts, one block reduction
+        int cnt = 0, bad = 0;
+        for (int q = threadIdx.x; q < nq; q += blockDim.x) {
+            int j = ix[q];
+            bad += j == UNSETTLED;
+            if (j >= 0 && distinct && (bits[words + (j >> 5)] >> (j & 31)) & 1u) j = -1;
+            cnt += j >= 0;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_xor(cnt, o); bad += __shfl_xor(bad, o); }
+        if (lane == 0) { sh[wid] = cnt; sh[16 + wid] = bad; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int run = 0, b = 0;
+            for (int i = 0; i < 16; ++i) { run += sh[i]; b += sh[16 + i]; }
+            if (b) atomicAdd(unsettled, b);
+            counts[p] = run;
+            keep[p] = run < min_count ? 0 : 1;
+        }
+        return;
     }
-    int64_t run = 0;
-    const int64_t base = MODE == 1 ? offsets[p] : 0;
-    for (int q0 = 0; q0 < nq; q0 += blockDim.x) {
+    // mode 1: rank within the wave by ballot, wave totals through LDS (two sets, by the round's
+    // parity: a wave is at most one round ahead of the slowest one, so one barrier per round)
+    int64_t run = offsets[p];
+    for (int q0 = 0, it = 0; q0 < nq; q0 += blockDim.x, it ^= 1) {
         const int q = q0 + threadIdx.x;
         int j = q < nq ? ix[q] : -1;
         if (j >= 0 && distinct && (bits[words + (j >> 5)] >> (j & 31)) & 1u) j = -1;
-        int total;
-        const int rank = block_exclusive_scan(j >= 0 ? 1 : 0, sh, total);
-        if (MODE == 1 && j >= 0) out[base + run + rank] = DMatchDev{q, j, 0, dx[q]};
+        const unsigned long long bal = __ballot(j >= 0);
+        if (lane == 0) sh[16 * it + wid] = __popcll(bal);
+        __syncthreads();
+        int wbase = 0, total = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int v = sh[16 * it + i];
+            wbase += i < wid ? v : 0;
+            total += v;
+        }
+        if (j >= 0) out[run + wbase + __popcll(bal & ((1ull << lane) - 1ull))] = DMatchDev{q, j, 0, dx[q]};
         run += total;
     }
-    if (MODE == 0 && threadIdx.x == 0) { counts[p] = run; keep[p] = run < min_count ? 0 : 1; }
 }
 
 // offsets[0..n] = exclusive scan of counts (single block, 1024 threads).
@@ -2025,12 +2092,11 @@ hipError_t launch_sift_knn2(const WorkItem* work, int n_work, const PairDev* pai
                             int32_t* qlist, int32_t* qcount, int n_pairs, const int32_t* porder, WorkItem* work2,
                             int32_t* work2_n, int32_t* out_idx,
                             float* out_dist, int2* slow_list, int32_t* slow_count, double ratio, hipStream_t st,
-                            hipEvent_t ev_screen, int32_t* qmask, unsigned long long* top2) {
+                            hipEvent_t ev_screen, int32_t* qmask, unsigned long long* top2, unsigned long long* slot1) {
     if (n_work == 0) return hipSuccess;
     const int v = sift_variant();
     if (v == 0 || v >= 101) {   // two-pass ratio test: screen every query, exact kernel on the rest
-        hipError_t e = hipMemsetAsync(qcount, 0, sizeof(int32_t) * (n_pairs + 8), st);   // + the screen's XCD tickets
-        if (e != hipSuccess) return e;
+        hipError_t e = hipSuccess;   // qcount and the screen's XCD tickets behind it: zeroed by the caller's one fill
         if (pass2_variant() == 10 && qmask && top2) {   // subset-restricted pass 2
             static const int slots = resident_slots(sift_screen16_kernel<8, 4, 2, 64, true, true>, 256);
             if (slots > 0 && persist_screens())
@@ -2044,9 +2110,9 @@ hipError_t launch_sift_knn2(const WorkItem* work, int n_work, const PairDev* pai
                 e = hipEventRecord(ev_screen, st);
                 if (e != hipSuccess) return e;
             }
-            sift_subset_kernel<4><<<n_pairs * 16, 256, 0, st>>>(pairs, imgs, desc8, norm, qlist, qmask, qcount, porder, top2);
+            sift_subset_kernel<4><<<n_pairs * 16, 256, 0, st>>>(pairs, imgs, desc8, norm, qlist, qmask, qcount, porder, top2, slot1);
             sift_settle_kernel<<<n_pairs, 256, 0, st>>>(pairs, imgs, qlist, qcount, top2, out_idx, out_dist, slow_list,
-                                                        slow_count, ratio);
+                                                        slow_count, ratio, qmask, slot1);
             return hipGetLastError();
         }
 #ifndef SFMX_DIAG
@@ -2136,10 +2202,9 @@ hipError_t launch_two_pass_overlap(bool sift, const MatchBatch* b, int nb, const
                                    int32_t* qlist, int32_t* qcount, int n_pairs, const int32_t* porder, int32_t* out_idx,
                                    float* out_dist, int2* slow_list, int32_t* slow_count, double ratio, hipStream_t st,
                                    hipEvent_t ev_screen, int32_t* qmask, unsigned long long* top2,
-                                   const OverlapStreams& os) {
+                                   unsigned long long* slot1, const OverlapStreams& os) {
     hipError_t e;
 #define OCHK(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
-    OCHK(hipMemsetAsync(qcount, 0, sizeof(int32_t) * n_pairs, st));
     OCHK(hipEventRecord(os.start, st));
     OCHK(hipStreamWaitEvent(os.sx, os.start, 0));
     OCHK(hipStreamWaitEvent(os.sp, os.start, 0));
@@ -2157,9 +2222,9 @@ hipError_t launch_two_pass_overlap(bool sift, const MatchBatch* b, int nb, const
         OCHK(hipEventRecord(os.screen[i], s));
         OCHK(hipStreamWaitEvent(os.sp, os.screen[i], 0));
         if (sift) {
-            sift_subset_kernel<4><<<B.np * 16, 256, 0, os.sp>>>(pairs, imgs, desc, norm, qlist, qmask, qcount, porder + B.p0, top2);
+            sift_subset_kernel<4><<<B.np * 16, 256, 0, os.sp>>>(pairs, imgs, desc, norm, qlist, qmask, qcount, porder + B.p0, top2, slot1);
             sift_settle_kernel<<<B.np, 256, 0, os.sp>>>(pairs, imgs, qlist, qcount, top2, out_idx, out_dist, slow_list,
-                                                        slow_count, ratio, porder + B.p0);
+                                                        slow_count, ratio, qmask, slot1, porder + B.p0);
         } else {
             orb_subset_kernel<4, 2><<<B.np * 16, 256, 0, os.sp>>>(pairs, imgs, (const uint8_t*)desc, qlist, qmask, qcount,
                                                                   porder + B.p0, top2);
@@ -2216,8 +2281,7 @@ hipError_t launch_orb_mfma(const WorkItem* work, int n_work, const PairDev* pair
                            unsigned long long* top2) {
     if (n_work == 0) return hipSuccess;
     if (orb_variant() == 0 || orb_variant() >= 10) {   // two-pass ratio test (default)
-        hipError_t e = hipMemsetAsync(qcount, 0, sizeof(int32_t) * (n_pairs + 8), st);   // + the screen's XCD tickets
-        if (e != hipSuccess) return e;
+        hipError_t e = hipSuccess;   // qcount and the screen's XCD tickets behind it: zeroed by the caller's one fill
         if (orb_variant() == 0 && qmask && top2) {   // subset-restricted pass 2 (default)
             static const int slots = resident_slots(orb_screen16_kernel<8, 4, 2, 64, true, true>, 256);
             if (slots > 0 && persist_screens())

@@ -38,7 +38,7 @@ hipError_t launch_prep_hamming(const uint8_t*, int, int, int, uint8_t*, hipStrea
 hipError_t launch_sift_knn2(const WorkItem*, int, const PairDev*, const ImgDev*, const int8_t*, const int32_t*,
                             const int32_t*, const int32_t*, int32_t*, int32_t*, int, const int32_t*, WorkItem*,
                             int32_t*, int32_t*, float*, int2*, int32_t*, double, hipStream_t, hipEvent_t, int32_t*,
-                            unsigned long long*);
+                            unsigned long long*, unsigned long long*);
 hipError_t launch_sift_slow(const int2*, const int32_t*, const PairDev*, const ImgDev*, const int8_t*,
                             const int32_t*, int32_t*, float*, double, hipStream_t);
 hipError_t launch_sift_f32(const WorkItem*, int, const PairDev*, const ImgDev*, const float*, int32_t*, float*,
@@ -55,7 +55,7 @@ int pass2_variant();
 hipError_t launch_two_pass_overlap(bool, const MatchBatch*, int, const WorkItem*, const PairDev*, const ImgDev*,
                                    const int8_t*, const int32_t*, const int32_t*, int32_t*, int32_t*, int, const int32_t*,
                                    int32_t*, float*, int2*, int32_t*, double, hipStream_t, hipEvent_t, int32_t*,
-                                   unsigned long long*, const OverlapStreams&);
+                                   unsigned long long*, unsigned long long*, const OverlapStreams&);
 hipError_t launch_selftest_sqrt(int64_t, uint32_t*, hipStream_t);
 int sift_variant();
 int sift_block_queries(int variant);
@@ -99,6 +99,11 @@ struct DevBuf {
         return SFMX_OK;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+// A typed view of memory another DevBuf owns.
+struct DevView {
+    void* p = nullptr;
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
@@ -161,11 +166,14 @@ struct sfmx_matcher {
     int n_pairs = 0;
     int64_t dense_total = 0;
     int64_t fp32_pairs = 0;
-    DevBuf pairs_d, work_d, work32_d, dense_idx, dense_dist, slow_list, slow_count, counts, keep, offsets, out;
+    DevBuf pairs_d, work_d, work32_d, dense_idx, dense_dist, slow_list, counts, keep, offsets, out;
     DevBuf qlist, qcount;   // two-pass SIFT path: per pair, the queries the screening pass could not settle
+    // One zeroed arena per run, a single fill: qcount[n_pairs] | the persistent screens' 8 XCD tickets |
+    // slow_count | unsettled (views into qcount's allocation, set by every run)
+    DevView slow_count;              // int32: length of slow_list
     DevBuf qmask, top2;     // subset pass 2: per forwarded query its row-subset mask; per query the merged top-2 keys
     DevBuf porder, work2, work2_n;   // pair order (by train image) and the compacted pass-2 work list
-    DevBuf unsettled;                // int32: pass-1 forwarded queries pass 2 never wrote (must stay 0)
+    DevView unsettled;               // int32: pass-1 forwarded queries pass 2 never wrote (must stay 0)
     DevBuf prep_tab;                 // batched SIFT prep: one PrepImg per image
     PinnedBuf stage_prep, stage_run, stage_imgs, stage_flags; // pinned staging of the small uploads / flag readback
     int32_t* hflags = nullptr;   // host-coherent mapped: integrality flags [hflags_cap] + sequence word (publish_flags_kernel)
@@ -266,13 +274,13 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
     const int row_bytes = (norm == SFMX_NORM_L2 || m->orb_fp4) ? SIFT_DIM : ORB_BYTES;
     int rc;
     if ((rc = m->desc8.ensure((size_t)row * row_bytes))) return rc;
-    if ((rc = m->flags.ensure(sizeof(int32_t) * std::max(n, 1)))) return rc;
+    if ((rc = m->flags.ensure(sizeof(int32_t) * align_up(std::max(n, 1), 64)))) return rc;
     if ((rc = m->imgs_d.ensure(sizeof(ImgDev) * std::max(n, 1)))) return rc;
     if (norm == SFMX_NORM_L2 && (rc = m->normv.ensure((size_t)row * 4))) return rc;
     if ((norm == SFMX_NORM_L2 || m->orb_fp4) && (rc = m->keyc.ensure((size_t)row * 4))) return rc;
     if (norm == SFMX_NORM_L2 && (rc = m->keyc2.ensure((size_t)row * 4))) return rc;
     if (!device_src && (rc = m->raw.ensure((size_t)raw_bytes))) return rc;
-    HIPCHK(hipMemsetAsync(m->flags.p, 0, sizeof(int32_t) * std::max(n, 1), st));
+    HIPCHK(hipMemsetAsync(m->flags.p, 0, sizeof(int32_t) * align_up(std::max(n, 1), 64), st));   // whole 256-B units: one dispatch
     std::vector<const void*> src(n);
     for (int i = 0; i < n; ++i) {
         const int64_t esz = norm == SFMX_NORM_L2 ? 4 : 1;
@@ -422,17 +430,16 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
         if ((rc = m->dense_idx.ensure(sizeof(int32_t) * std::max<int64_t>(dense, 1)))) return rc;
         if ((rc = m->dense_dist.ensure(sizeof(float) * std::max<int64_t>(dense, 1)))) return rc;
         if ((rc = m->slow_list.ensure(sizeof(int2) * std::max<int64_t>(dense, 1)))) return rc;
-        if ((rc = m->slow_count.ensure(sizeof(int32_t)))) return rc;
         if ((rc = m->qlist.ensure(sizeof(int32_t) * std::max<int64_t>(dense, 1)))) return rc;
         if (m->norm == SFMX_NORM_L2 || m->orb_fp4) {
             if ((rc = m->qmask.ensure(sizeof(int32_t) * std::max<int64_t>(dense, 1)))) return rc;
             if ((rc = m->top2.ensure(2 * sizeof(uint64_t) * std::max<int64_t>(dense, 1)))) return rc;
         }
-        if ((rc = m->qcount.ensure(sizeof(int32_t) * (n_pairs + 8)))) return rc;   // + the persistent screens' XCD tickets
+        if ((rc = m->qcount.ensure(sizeof(int32_t) * align_up(n_pairs + 8 + 2, 64)))) return rc;   // the run's zeroed arena (see qcount)
+        m->slow_count.p = m->unsettled.p = nullptr;   // views of the old allocation; set again below
         if ((rc = m->porder.ensure(sizeof(int32_t) * std::max(n_pairs, 1)))) return rc;
         if ((rc = m->work2.ensure(sizeof(WorkItem) * std::max<size_t>(4 * work.size(), 1)))) return rc;   // pass-2 items >= 128 queries
         if ((rc = m->work2_n.ensure(sizeof(int32_t)))) return rc;
-        if ((rc = m->unsettled.ensure(sizeof(int32_t)))) return rc;
         if ((rc = m->counts.ensure(sizeof(int64_t) * std::max(n_pairs, 1)))) return rc;
         if ((rc = m->keep.ensure(sizeof(int32_t) * std::max(n_pairs, 1)))) return rc;
         if ((rc = m->offsets.ensure(sizeof(int64_t) * (n_pairs + 1)))) return rc;
@@ -489,8 +496,10 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
             for (auto& e : set) HIPCHK(hipEventCreate(&e));
     m->ev = m->evr[m->runs % sfmx_matcher::EV_RING];
     ++m->runs;
-    HIPCHK(hipMemsetAsync(m->slow_count.p, 0, sizeof(int32_t), st));
-    HIPCHK(hipMemsetAsync(m->unsettled.p, 0, sizeof(int32_t), st));
+    m->slow_count.p = m->qcount.as<int32_t>() + n_pairs + 8;
+    m->unsettled.p = m->qcount.as<int32_t>() + n_pairs + 9;
+    // the run's only fill; whole 256-B units, which the runtime clears in one dispatch (no unaligned tail)
+    HIPCHK(hipMemsetAsync(m->qcount.p, 0, sizeof(int32_t) * align_up(n_pairs + 8 + 2, 64), st));
     HIPCHK(hipEventRecord(m->ev[0], st));
     HIPCHK(hipEventRecord(m->ev[3], st));   // re-recorded after pass 1 by the two-pass launchers
     // Pairs with an empty left image have no work item; pairs with an empty
@@ -523,7 +532,7 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
                                        m->qcount.as<int32_t>(), n_pairs, m->porder.as<int32_t>(),
                                        m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), m->slow_list.as<int2>(),
                                        m->slow_count.as<int32_t>(), ratio, st, m->ev[3], m->qmask.as<int32_t>(),
-                                       m->top2.as<unsigned long long>(), os));
+                                       m->top2.as<unsigned long long>(), m->out.as<unsigned long long>(), os));
         HIPCHK(hipEventRecord(m->ev[1], st));
         if (sift) {
             HIPCHK(launch_sift_slow(m->slow_list.as<int2>(), m->slow_count.as<int32_t>(), P, I, m->desc8.as<int8_t>(),
@@ -538,7 +547,8 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
                                 m->qlist.as<int32_t>(), m->qcount.as<int32_t>(), n_pairs, m->porder.as<int32_t>(),
                                 m->work2.as<WorkItem>(), m->work2_n.as<int32_t>(), m->dense_idx.as<int32_t>(),
                                 m->dense_dist.as<float>(), m->slow_list.as<int2>(), m->slow_count.as<int32_t>(), ratio, st,
-                                m->ev[3], m->qmask.as<int32_t>(), m->top2.as<unsigned long long>()));
+                                m->ev[3], m->qmask.as<int32_t>(), m->top2.as<unsigned long long>(),
+                                m->out.as<unsigned long long>()));   // pass 2's second slot: `out` is idle until assembly
         HIPCHK(hipEventRecord(m->ev[1], st));
         HIPCHK(launch_sift_slow(m->slow_list.as<int2>(), m->slow_count.as<int32_t>(), P, I, m->desc8.as<int8_t>(),
                                 m->normv.as<int32_t>(), m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), ratio, st));
@@ -721,8 +731,8 @@ int sfmx_matcher_destroy(sfmx_matcher* m) {
         if (m->hflags) (void)hipHostFree(m->hflags);
         m->hflags = nullptr;
         DevBuf* bufs[] = {&m->raw, &m->desc8, &m->normv, &m->keyc, &m->keyc2, &m->qlist, &m->qcount, &m->porder, &m->work2, &m->work2_n, &m->f32, &m->flags, &m->imgs_d, &m->pairs_d, &m->prep_tab,
-                          &m->work_d, &m->work32_d, &m->dense_idx, &m->dense_dist, &m->slow_list, &m->slow_count,
-                          &m->unsettled, &m->counts, &m->keep, &m->offsets, &m->out};
+                          &m->work_d, &m->work32_d, &m->dense_idx, &m->dense_dist, &m->slow_list,
+                          &m->counts, &m->keep, &m->offsets, &m->out};
         for (DevBuf* b : bufs) b->release();
         for (auto& set : m->evr)
             for (auto& e : set) if (e) (void)hipEventDestroy(e);
