@@ -40,6 +40,18 @@ struct PairDev {
     int64_t dense_base;    // offset of this pair's per-query results (sum of previous Nq)
 };
 
+// One pair of a run as a flat record, in `porder` order (built by the host with the plan): what the
+// list-path kernels would otherwise chain through porder -> pairs -> imgs (three dependent loads).
+struct PairRec {
+    int64_t lrow0, rrow0;  // first pool row of the left (query) / right (train) image
+    int64_t dense_base;    // as PairDev
+    int32_t nq, nt;        // real rows of the left / right image
+    int32_t rows_pad;      // padded rows of the right image
+    int32_t pair;          // index in the caller's pair list
+    int32_t lists;         // 1: settled and assembled from the forwarded lists; 0: through the dense arrays
+    int32_t _pad;
+};
+
 struct WorkItem {          // one 512-query block of one pair
     int32_t pair;
     int32_t q0;

@@ -612,7 +612,10 @@ __device__ __forceinline__ int xcd_ticket(int32_t* ticket, int n) {
 // PERSIST (r04, diagnostic build only, see persist_screens): a grid of resident workgroup slots takes work items
 // from a ticket counter in list order (the last partial round of a one-item-per-workgroup grid --
 // C2: 19 600 items on 512 slots, 38.3 rounds -- becomes a ragged end of single items).
-template <int QT, int WAVES, int MINW, int STAGE, bool SUBSET = false, bool PERSIST = false>
+// LISTS (the product path, with SUBSET): nothing goes to the dense per-query arrays.  A rejected query
+// leaves no trace, a forwarded one is its list entry alone, and its pass-2 state (top2 / slot1) lives at
+// its list slot (dense_base + slot), where sift_subset_kernel<_, true> and sift_finish_kernel find it.
+template <int QT, int WAVES, int MINW, int STAGE, bool SUBSET = false, bool PERSIST = false, bool LISTS = false>
 __global__ __launch_bounds__(WAVES * 64, MINW)
 void sift_screen16_kernel(const WorkItem* __restrict__ work, const PairDev* __restrict__ pairs,
                           const ImgDev* __restrict__ imgs, const int8_t* __restrict__ desc8,
@@ -744,7 +747,10 @@ void sift_screen16_kernel(const WorkItem* __restrict__ work, const PairDev* __re
         const int qi = qbase + qt * 16 + l16;
         if (g != 0 || qi >= nq) continue;
         const int64_t o = P.dense_base + qi;
-        if (nt == 0) { out_idx[o] = -1; out_dist[o] = 0.f; continue; }
+        if (nt == 0) {
+            if constexpr (!LISTS) { out_idx[o] = -1; out_dist[o] = 0.f; }
+            continue;
+        }
         bool reject = false;
         if (nt >= 2 && k2 >= KEY_VALID) {
             const int64_t na = norm[L.row0 + qi];
@@ -752,17 +758,20 @@ void sift_screen16_kernel(const WorkItem* __restrict__ work, const PairDev* __re
             reject = !((double)sqrt_rn_int(s1) < (double)sqrt_rn_int(s2) * ratio);
         }
         if (reject) {
-            out_idx[o] = -1;
-            out_dist[o] = 0.f;
+            if constexpr (!LISTS) { out_idx[o] = -1; out_dist[o] = 0.f; }
         } else {
             const int slot = atomicAdd(&qcount[w.pair], 1);
             qlist[P.dense_base + slot] = qi;
             if constexpr (SUBSET) {
                 qmask[P.dense_base + slot] = mask;
-                top2[2 * o] = ~0ull;
-                top2[2 * o + 1] = ~0ull;
+                // a two-subset mask: both 16-B words are written whole by plain stores (sift_subset_kernel)
+                const int64_t t = LISTS ? P.dense_base + slot : o;
+                if (!LISTS || __popc(mask) != 2) {
+                    top2[2 * t] = ~0ull;
+                    top2[2 * t + 1] = ~0ull;
+                }
             }
-            out_idx[o] = UNSETTLED;   // pass 2 must overwrite it (assemble counts survivors)
+            if constexpr (!LISTS) out_idx[o] = UNSETTLED;   // pass 2 must overwrite it (assemble counts survivors)
         }
     }
     __syncthreads();   // the next item restages the LDS buffers and rewrites item_sh
@@ -805,7 +814,11 @@ void sift_screen16_kernel(const WorkItem* __restrict__ work, const PairDev* __re
 // that are real rows (r < nt), and the query is in its pair's list (cnt > 0).  The workgroup then
 // ends on plain stores instead of waiting for a returning atomic.  Every other mask (3+ subsets,
 // or all 16 when the screen's bound was not usable) takes the atomics above.
-template <int WAVES>
+//
+// LISTS (the product path): the query's pass-2 state lives at its list slot, dense_base + e, not at
+// its row: the gather carries e (16 bits, relative to the window) beside the packed row | mode, and
+// sift_finish_kernel walks the same slots in order instead of two scattered 16-B reads per query.
+template <int WAVES, bool LISTS = false>
 __global__ __launch_bounds__(WAVES * 64, 2)
 void sift_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restrict__ imgs,
                         const int8_t* __restrict__ desc8, const int32_t* __restrict__ norm,
@@ -821,9 +834,10 @@ void sift_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restr
     __shared__ __attribute__((aligned(16))) char rows_lds[CH * SIFT_DIM];
     __shared__ int keys_lds[CH];
     __shared__ int ql[WIN];
+    __shared__ unsigned short qs[LISTS ? WIN : 2];   // LISTS: the entry's list slot, relative to the window
     __shared__ int s_n;
     // four workgroups per CU (160 KB of LDS), as the 128-VGPR bound of four waves per SIMD allows
-    static_assert(sizeof(rows_lds) + sizeof(keys_lds) + sizeof(ql) + sizeof(s_n) <= 160 * 1024 / 4,
+    static_assert(sizeof(rows_lds) + sizeof(keys_lds) + sizeof(ql) + sizeof(qs) + sizeof(s_n) <= 160 * 1024 / 4,
                   "pass-2 LDS must leave four workgroups resident per CU");
 
     const int tid = threadIdx.x, wid = tid >> 6, lane = tid & 63, h = lane >> 5, l32 = lane & 31;
@@ -864,7 +878,9 @@ void sift_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restr
             const int mk = qms[e];
             if ((mk >> r) & 1) {   // query row (< 2^18) | merge mode << 20: 0 atomics, 1 / 2 the lower / upper of two subsets
                 const int mode = __popc(mk) == 2 ? ((mk & ((1 << r) - 1)) ? 2 : 1) : 0;
-                ql[atomicAdd(&s_n, 1)] = qls[e] | (mode << 20);
+                const int at = atomicAdd(&s_n, 1);
+                ql[at] = qls[e] | (mode << 20);
+                if constexpr (LISTS) qs[at] = (unsigned short)(e - e0);
             }
         }
         __syncthreads();
@@ -873,6 +889,8 @@ void sift_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restr
             const int qe = g0 + wid * 32 + l32;
             const int qpk = qe < n ? ql[qe] : -1;
             const int qrow = qpk < 0 ? -1 : (qpk & 0xFFFFF), mode = qpk < 0 ? 0 : (qpk >> 20);
+            int qslot = qrow;          // where the query's pass-2 state lives: its row, or (LISTS) its list slot
+            if constexpr (LISTS) qslot = qe < n ? e0 + qs[qe] : 0;
             const bool active = g0 + wid * 32 < n;   // wave-uniform
             const int64_t lrow = L.row0 + (qrow < 0 ? 0 : qrow);
             i32x4 bq[4];
@@ -941,10 +959,10 @@ void sift_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restr
                 const unsigned long long k1 = T1 != INT_MAX ? ((unsigned long long)(na + T1) << 32) | (unsigned)(r + 16 * J1) : ~0ull;
                 const unsigned long long k2 = T2 != INT_MAX ? ((unsigned long long)(na + T2) << 32) | (unsigned)(r + 16 * J2) : ~0ull;
                 if (mode != 0) {          // one of exactly two subsets: its own 16-B slot, no atomics
-                    unsigned long long* b = (mode == 1 ? top2 : slot1) + 2 * (P.dense_base + qrow);
+                    unsigned long long* b = (mode == 1 ? top2 : slot1) + 2 * (P.dense_base + qslot);
                     *reinterpret_cast<ulonglong2*>(b) = make_ulonglong2(k1, k2);
                 } else if (T1 != INT_MAX) {
-                    unsigned long long* b = top2 + 2 * (P.dense_base + qrow);
+                    unsigned long long* b = top2 + 2 * (P.dense_base + qslot);
                     if (T2 != INT_MAX) atomicMin(b + 1, k2);
                     const unsigned long long old = atomicMin(b, k1);
                     atomicMin(b + 1, old > k1 ? old : k1);
@@ -1073,6 +1091,34 @@ __device__ __forceinline__ void top2_u64(unsigned long long k, unsigned long lon
     if (k < b2) { if (k < b1) { b2 = b1; b1 = k; } else b2 = k; }
 }
 
+// One wave: query row `lrow` of the pool against train rows [rrow0, rrow0 + nt); every lane ends with
+// the two smallest (sqrtf bits << 32 | j) keys.
+__device__ __forceinline__ void slow_top2(const int8_t* __restrict__ desc8, const int32_t* __restrict__ norm,
+                                          int64_t lrow, int64_t rrow0, int nt, int lane,
+                                          unsigned long long& b1, unsigned long long& b2) {
+    const int* q = reinterpret_cast<const int*>(desc8 + lrow * SIFT_DIM);
+    int qw[32];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) qw[k] = q[k];
+    const int na = norm[lrow];
+    b1 = ~0ull;
+    b2 = ~0ull;
+    for (int j = lane; j < nt; j += 64) {
+        const int* t = reinterpret_cast<const int*>(desc8 + (rrow0 + j) * SIFT_DIM);
+        int dot = 0;
+#pragma unroll
+        for (int k = 0; k < 32; ++k) dot = __builtin_amdgcn_sdot4(qw[k], t[k], dot, false);
+        const int64_t s = (int64_t)na + norm[rrow0 + j] - 2 * (int64_t)dot;
+        const float d = sqrt_rn_int(s);
+        top2_u64(((unsigned long long)__float_as_uint(d) << 32) | (unsigned)j, b1, b2);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long p1 = __shfl_xor(b1, o), p2 = __shfl_xor(b2, o);
+        top2_u64(p1, b1, b2);
+        top2_u64(p2, b1, b2);
+    }
+}
+
 __global__ __launch_bounds__(256)
 void sift_slow_kernel(const int2* __restrict__ slow_list, const int32_t* __restrict__ slow_count,
                       const PairDev* __restrict__ pairs, const ImgDev* __restrict__ imgs,
@@ -1085,26 +1131,8 @@ void sift_slow_kernel(const int2* __restrict__ slow_list, const int32_t* __restr
         const int2 it = slow_list[e];
         const PairDev P = pairs[it.x];
         const ImgDev L = imgs[P.left], R = imgs[P.right];
-        const int* q = reinterpret_cast<const int*>(desc8 + (L.row0 + it.y) * SIFT_DIM);
-        int qw[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) qw[k] = q[k];
-        const int na = norm[L.row0 + it.y];
-        unsigned long long b1 = ~0ull, b2 = ~0ull;
-        for (int j = lane; j < R.rows; j += 64) {
-            const int* t = reinterpret_cast<const int*>(desc8 + (R.row0 + j) * SIFT_DIM);
-            int dot = 0;
-#pragma unroll
-            for (int k = 0; k < 32; ++k) dot = __builtin_amdgcn_sdot4(qw[k], t[k], dot, false);
-            const int64_t s = (int64_t)na + norm[R.row0 + j] - 2 * (int64_t)dot;
-            const float d = sqrt_rn_int(s);
-            top2_u64(((unsigned long long)__float_as_uint(d) << 32) | (unsigned)j, b1, b2);
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long p1 = __shfl_xor(b1, o), p2 = __shfl_xor(b2, o);
-            top2_u64(p1, b1, b2);
-            top2_u64(p2, b1, b2);
-        }
+        unsigned long long b1, b2;
+        slow_top2(desc8, norm, L.row0 + it.y, R.row0, R.rows, lane, b1, b2);
         if (lane == 0) {
             const float d1 = __uint_as_float((unsigned)(b1 >> 32)), d2 = __uint_as_float((unsigned)(b2 >> 32));
             const int64_t o = P.dense_base + it.y;
@@ -1919,58 +1947,52 @@ void orb_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restric
 // keep flag (SfM.cpp:566-570), then a second launch writes packed DMatch in
 // query order at the scanned pair offset.
 // mode 0: count -> counts[p], keep[p];  mode 1: write packed matches.
-template <int MODE>
-__global__ __launch_bounds__(1024)
-void assemble_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restrict__ imgs,
-                     const int32_t* __restrict__ out_idx, const float* __restrict__ out_dist,
-                     int distinct, int min_count, int64_t* __restrict__ counts, int32_t* __restrict__ keep,
-                     const int64_t* __restrict__ offsets, DMatchDev* __restrict__ out, int32_t* __restrict__ unsettled) {
-    extern __shared__ __attribute__((aligned(16))) unsigned bits[];   // seen | dup bitsets (distinct only)
-    __shared__ int sh[32];
-    const int p = blockIdx.x;
-    const PairDev P = pairs[p];
-    const int nq = imgs[P.left].rows, nt = imgs[P.right].rows;
-    const int words = (nt + 31) >> 5;
-    const int32_t* ix = out_idx + P.dense_base;
-    const float* dx = out_dist + P.dense_base;
-    if (distinct) {
-        for (int i = threadIdx.x; i < 2 * words; i += blockDim.x) bits[i] = 0;
-        __syncthreads();
-        for (int q = threadIdx.x; q < nq; q += blockDim.x) {
-            const int j = ix[q];
-            if (j >= 0) {
-                const unsigned bit = 1u << (j & 31);
-                const unsigned old = atomicOr(&bits[j >> 5], bit);
-                if (old & bit) atomicOr(&bits[words + (j >> 5)], bit);
-            }
-        }
-        __syncthreads();
+// The pieces are device functions (blocks of 1024 threads = 16 waves) shared with the list-path
+// kernels below, which run them for the pairs that go through the dense arrays.
+__device__ __forceinline__ void mark_seen(unsigned* bits, int words, int j) {   // seen | dup bitsets
+    const unsigned bit = 1u << (j & 31);
+    const unsigned old = atomicOr(&bits[j >> 5], bit);
+    if (old & bit) atomicOr(&bits[words + (j >> 5)], bit);
+}
+__device__ __forceinline__ void dense_dup_bits(unsigned* bits, const int32_t* __restrict__ ix, int nq, int words) {
+    for (int i = threadIdx.x; i < 2 * words; i += blockDim.x) bits[i] = 0;
+    __syncthreads();
+    for (int q = threadIdx.x; q < nq; q += blockDim.x) {
+        const int j = ix[q];
+        if (j >= 0) mark_seen(bits, words, j);
     }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;   // 1024 threads = 16 waves
-    if (MODE == 0) {   // one read of the pair's results: per-thread counts, one block reduction
-        int cnt = 0, bad = 0;
-        for (int q = threadIdx.x; q < nq; q += blockDim.x) {
-            int j = ix[q];
-            bad += j == UNSETTLED;
-            if (j >= 0 && distinct && (bits[words + (j >> 5)] >> (j & 31)) & 1u) j = -1;
-            cnt += j >= 0;
-        }
+    __syncthreads();
+}
+// one read of the pair's results: per-thread counts, one block reduction
+__device__ __forceinline__ void dense_count(const unsigned* bits, int* sh, const int32_t* __restrict__ ix, int nq, int words,
+                                            int distinct, int min_count, int p, int64_t* __restrict__ counts,
+                                            int32_t* __restrict__ keep, int32_t* __restrict__ unsettled) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int cnt = 0, bad = 0;
+    for (int q = threadIdx.x; q < nq; q += blockDim.x) {
+        int j = ix[q];
+        bad += j == UNSETTLED;
+        if (j >= 0 && distinct && (bits[words + (j >> 5)] >> (j & 31)) & 1u) j = -1;
+        cnt += j >= 0;
+    }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_xor(cnt, o); bad += __shfl_xor(bad, o); }
-        if (lane == 0) { sh[wid] = cnt; sh[16 + wid] = bad; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int run = 0, b = 0;
-            for (int i = 0; i < 16; ++i) { run += sh[i]; b += sh[16 + i]; }
-            if (b) atomicAdd(unsettled, b);
-            counts[p] = run;
-            keep[p] = run < min_count ? 0 : 1;
-        }
-        return;
+    for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_xor(cnt, o); bad += __shfl_xor(bad, o); }
+    if (lane == 0) { sh[wid] = cnt; sh[16 + wid] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0, b = 0;
+        for (int i = 0; i < 16; ++i) { run += sh[i]; b += sh[16 + i]; }
+        if (b) atomicAdd(unsettled, b);
+        counts[p] = run;
+        keep[p] = run < min_count ? 0 : 1;
     }
-    // mode 1: rank within the wave by ballot, wave totals through LDS (two sets, by the round's
-    // parity: a wave is at most one round ahead of the slowest one, so one barrier per round)
-    int64_t run = offsets[p];
+}
+// rank within the wave by ballot, wave totals through LDS (two sets, by the round's
+// parity: a wave is at most one round ahead of the slowest one, so one barrier per round)
+__device__ __forceinline__ void dense_write(const unsigned* bits, int* sh, const int32_t* __restrict__ ix,
+                                            const float* __restrict__ dx, int nq, int words, int distinct, int64_t run,
+                                            DMatchDev* __restrict__ out) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     for (int q0 = 0, it = 0; q0 < nq; q0 += blockDim.x, it ^= 1) {
         const int q = q0 + threadIdx.x;
         int j = q < nq ? ix[q] : -1;
@@ -1987,6 +2009,209 @@ void assemble_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restrict
         }
         if (j >= 0) out[run + wbase + __popcll(bal & ((1ull << lane) - 1ull))] = DMatchDev{q, j, 0, dx[q]};
         run += total;
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(1024)
+void assemble_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restrict__ imgs,
+                     const int32_t* __restrict__ out_idx, const float* __restrict__ out_dist,
+                     int distinct, int min_count, int64_t* __restrict__ counts, int32_t* __restrict__ keep,
+                     const int64_t* __restrict__ offsets, DMatchDev* __restrict__ out, int32_t* __restrict__ unsettled) {
+    extern __shared__ __attribute__((aligned(16))) unsigned bits[];   // seen | dup bitsets (distinct only)
+    __shared__ int sh[32];
+    const int p = blockIdx.x;
+    const PairDev P = pairs[p];
+    const int nq = imgs[P.left].rows, nt = imgs[P.right].rows;
+    const int words = (nt + 31) >> 5;
+    const int32_t* ix = out_idx + P.dense_base;
+    if (distinct) dense_dup_bits(bits, ix, nq, words);
+    if (MODE == 0) dense_count(bits, sh, ix, nq, words, distinct, min_count, p, counts, keep, unsettled);
+    else dense_write(bits, sh, ix, out_dist + P.dense_base, nq, words, distinct, offsets[p], out);
+}
+
+// ---------------------------------------------------------------------------
+// List path (product SIFT): settle and assemble from the forwarded lists.  Only a query the screen
+// forwarded can become a match, and its whole state sits at its list slot e (qlist, qmask, top2,
+// slot1 at dense_base + e), so nothing below touches a per-row array.  One 1024-thread workgroup per
+// pair, from the pair's flat record; a pair whose record says lists = 0 (fp32 fallback) is counted
+// and written from the dense arrays by the functions above, so one run can hold both kinds.
+//
+// sift_finish_kernel, per slot: merge the two-slot or atomic top-2 (see sift_subset_kernel), Lowe's
+// test, and the result (j or -1, distance bits) over the first 8 B of the slot's top2 word.  Queries
+// in the float-sqrt collision range are listed (in the pair's part of slow_list) and re-ranked after
+// a barrier, one wave each.  Then the distinct filter and the count: with the seen / dup bitsets a
+// train row is matched exactly once iff seen and not dup, so the count is a popcount over the words.
+// A slot pass 2 never wrote counts as unsettled (the run fails in fetch / stats).
+__global__ __launch_bounds__(1024)
+void sift_finish_kernel(const PairRec* __restrict__ recs, const int32_t* __restrict__ qlist,
+                        const int32_t* __restrict__ qmask, const int32_t* __restrict__ qcount,
+                        unsigned long long* __restrict__ top2, const unsigned long long* __restrict__ slot1,
+                        int2* __restrict__ slow_list, int32_t* __restrict__ slow_count,
+                        const int8_t* __restrict__ desc8, const int32_t* __restrict__ norm,
+                        const int32_t* __restrict__ out_idx, double ratio, int distinct, int min_count,
+                        int64_t* __restrict__ counts, int32_t* __restrict__ keep, int32_t* __restrict__ unsettled) {
+    extern __shared__ __attribute__((aligned(16))) unsigned bits[];   // seen | dup bitsets (distinct only)
+    __shared__ int sh[32];
+    __shared__ int s_slow;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const PairRec R = recs[blockIdx.x];
+    const int nt = R.nt, words = (nt + 31) >> 5;
+    if (!R.lists) {
+        const int32_t* ix = out_idx + R.dense_base;
+        if (distinct) dense_dup_bits(bits, ix, R.nq, words);
+        dense_count(bits, sh, ix, R.nq, words, distinct, min_count, R.pair, counts, keep, unsettled);
+        return;
+    }
+    const int cnt = qcount[R.pair];
+    if (cnt == 0) {
+        if (tid == 0) { counts[R.pair] = 0; keep[R.pair] = 0 < min_count ? 0 : 1; }
+        return;
+    }
+    if (tid == 0) s_slow = 0;
+    if (distinct)
+        for (int i = tid; i < 2 * words; i += 1024) bits[i] = 0;
+    __syncthreads();
+    const int32_t* qls = qlist + R.dense_base;
+    const int32_t* qms = qmask + R.dense_base;
+    unsigned long long* t2 = top2 + 2 * R.dense_base;
+    const unsigned long long* s1p = slot1 + 2 * R.dense_base;
+    int2* sl = slow_list + R.dense_base;
+    int acc = 0, bad = 0;
+    for (int e = tid; e < cnt; e += 1024) {
+        const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(t2 + 2 * e);
+        unsigned long long b0 = a.x, b1 = a.y;
+        if (__popc(qms[e]) == 2) {   // two subsets, one 16-B word each: merge the two top-2
+            const ulonglong2 c = *reinterpret_cast<const ulonglong2*>(s1p + 2 * e);
+            const unsigned long long lo = b0 < c.x ? b0 : c.x, hi = b0 < c.x ? c.x : b0, m2 = b1 < c.y ? b1 : c.y;
+            b0 = lo;
+            b1 = hi < m2 ? hi : m2;
+        }
+        int j = -1;
+        float d1 = 0.f;
+        if (b0 == ~0ull || (nt >= 2 && b1 == ~0ull)) {
+            bad += nt != 0;   // pass 2 left a flagged subset unscanned
+        } else {
+            const int64_t s1 = (int64_t)(b0 >> 32), s2 = (int64_t)(b1 >> 32);
+            if (nt >= 2 && s2 >= SQRT_SAFE) {
+                sl[atomicAdd(&s_slow, 1)] = make_int2(e, qls[e]);
+                continue;
+            }
+            d1 = sqrt_rn_int(s1);
+            j = lowe_select((int)(b0 & 0xffffffffu), d1, nt >= 2 ? sqrt_rn_int(s2) : 0.f, nt, ratio);
+        }
+        *reinterpret_cast<int2*>(t2 + 2 * e) = make_int2(j, __float_as_int(d1));
+        if (j >= 0) {
+            if (distinct) mark_seen(bits, words, j);
+            else ++acc;
+        }
+    }
+    __syncthreads();
+    const int n_slow = s_slow;
+    for (int k = wid; k < n_slow; k += 16) {   // exact float-sqrt ranking, one wave per query
+        const int2 it = sl[k];
+        unsigned long long b1, b2;
+        slow_top2(desc8, norm, R.lrow0 + it.y, R.rrow0, nt, lane, b1, b2);
+        if (lane == 0) {
+            const float d1 = __uint_as_float((unsigned)(b1 >> 32)), d2 = __uint_as_float((unsigned)(b2 >> 32));
+            const int j = lowe_select((int)(b1 & 0xffffffffu), d1, d2, 2, ratio);   // slow path implies nt >= 2
+            *reinterpret_cast<int2*>(t2 + 2 * it.x) = make_int2(j, __float_as_int(d1));
+            if (j >= 0) {
+                if (distinct) mark_seen(bits, words, j);
+                else ++acc;
+            }
+        }
+    }
+    if (distinct) {
+        __syncthreads();
+        for (int i = tid; i < words; i += 1024) acc += __popc(bits[i] & ~bits[words + i]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { acc += __shfl_xor(acc, o); bad += __shfl_xor(bad, o); }
+    if (lane == 0) { sh[wid] = acc; sh[16 + wid] = bad; }
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0, b = 0;
+        for (int i = 0; i < 16; ++i) { run += sh[i]; b += sh[16 + i]; }
+        if (b) atomicAdd(unsettled, b);
+        if (n_slow) atomicAdd(slow_count, n_slow);
+        counts[R.pair] = run;
+        keep[R.pair] = run < min_count ? 0 : 1;
+    }
+}
+
+// assemble_lists_kernel: the pair's accepted slots -> packed DMatch at offsets[pair], in ascending
+// query order whatever order the screen's atomics filled the list in: a bitmap of the accepted
+// query rows in LDS (nq bits) with per-word prefix counts ranks each slot's query.
+// LDS: bitmap[W] | prefix[W] | seen[words] | dup[words] (the last two with distinct only).
+__global__ __launch_bounds__(1024)
+void assemble_lists_kernel(const PairRec* __restrict__ recs, const int32_t* __restrict__ qlist,
+                           const int32_t* __restrict__ qcount, const unsigned long long* __restrict__ top2,
+                           const int32_t* __restrict__ out_idx, const float* __restrict__ out_dist, int distinct,
+                           const int64_t* __restrict__ counts, const int64_t* __restrict__ offsets,
+                           DMatchDev* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned bits[];
+    __shared__ int sh[32];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const PairRec R = recs[blockIdx.x];
+    const int words = (R.nt + 31) >> 5;
+    if (!R.lists) {
+        const int32_t* ix = out_idx + R.dense_base;
+        if (distinct) dense_dup_bits(bits, ix, R.nq, words);
+        dense_write(bits, sh, ix, out_dist + R.dense_base, R.nq, words, distinct, offsets[R.pair], out);
+        return;
+    }
+    const int cnt = qcount[R.pair];
+    if (cnt == 0 || counts[R.pair] == 0) return;
+    const int W = (R.nq + 31) >> 5;
+    unsigned* bm = bits;
+    unsigned* pre = bits + W;
+    unsigned* seen = bits + 2 * W;
+    for (int i = tid; i < W; i += 1024) bm[i] = 0;
+    if (distinct)
+        for (int i = tid; i < 2 * words; i += 1024) seen[i] = 0;
+    __syncthreads();
+    const int32_t* qls = qlist + R.dense_base;
+    const int2* res = reinterpret_cast<const int2*>(top2 + 2 * R.dense_base);   // slot e: res[2 e] = (j, distance bits)
+    if (distinct) {
+        for (int e = tid; e < cnt; e += 1024) {
+            const int j = res[2 * e].x;
+            if (j >= 0) mark_seen(seen, words, j);
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < cnt; e += 1024) {
+        const int j = res[2 * e].x;
+        if (j >= 0 && !(distinct && ((seen[words + (j >> 5)] >> (j & 31)) & 1u))) {
+            const int qi = qls[e];
+            atomicOr(&bm[qi >> 5], 1u << (qi & 31));
+        }
+    }
+    __syncthreads();
+    {   // exclusive prefix of the words' popcounts: each thread a contiguous run of words
+        const int per = (W + 1023) / 1024, w0 = min(tid * per, W), w1 = min(w0 + per, W);
+        int mine = 0;
+        for (int w = w0; w < w1; ++w) mine += __popc(bm[w]);
+        int incl = mine;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(incl, o);
+            if (lane >= o) incl += v;
+        }
+        if (lane == 63) sh[wid] = incl;
+        __syncthreads();
+        int at = incl - mine;
+        for (int i = 0; i < wid; ++i) at += sh[i];
+        for (int w = w0; w < w1; ++w) { pre[w] = at; at += __popc(bm[w]); }
+    }
+    __syncthreads();
+    DMatchDev* o = out + offsets[R.pair];
+    for (int e = tid; e < cnt; e += 1024) {
+        const int2 r = res[2 * e];
+        if (r.x >= 0 && !(distinct && ((seen[words + (r.x >> 5)] >> (r.x & 31)) & 1u))) {
+            const int qi = qls[e];
+            const unsigned below = bm[qi >> 5] & ((1u << (qi & 31)) - 1u);
+            o[pre[qi >> 5] + __popc(below)] = DMatchDev{qi, r.x, 0, __int_as_float(r.y)};
+        }
     }
 }
 
@@ -2092,11 +2317,24 @@ hipError_t launch_sift_knn2(const WorkItem* work, int n_work, const PairDev* pai
                             int32_t* qlist, int32_t* qcount, int n_pairs, const int32_t* porder, WorkItem* work2,
                             int32_t* work2_n, int32_t* out_idx,
                             float* out_dist, int2* slow_list, int32_t* slow_count, double ratio, hipStream_t st,
-                            hipEvent_t ev_screen, int32_t* qmask, unsigned long long* top2, unsigned long long* slot1) {
+                            hipEvent_t ev_screen, int32_t* qmask, unsigned long long* top2, unsigned long long* slot1,
+                            bool lists) {
     if (n_work == 0) return hipSuccess;
     const int v = sift_variant();
     if (v == 0 || v >= 101) {   // two-pass ratio test: screen every query, exact kernel on the rest
         hipError_t e = hipSuccess;   // qcount and the screen's XCD tickets behind it: zeroed by the caller's one fill
+        if (lists) {   // product path: pass-2 state at the list slots; the caller settles with launch_finish_lists
+            if (v != 0 || pass2_variant() != 10 || !qmask || !top2) return hipErrorInvalidValue;
+            sift_screen16_kernel<8, 4, 2, 64, true, false, true><<<n_work, 256, 0, st>>>(
+                work, pairs, imgs, desc8, norm, keyc2, out_idx, out_dist, qlist, qcount, ratio, qmask, top2);
+            if (ev_screen) {
+                e = hipEventRecord(ev_screen, st);
+                if (e != hipSuccess) return e;
+            }
+            sift_subset_kernel<4, true><<<n_pairs * 16, 256, 0, st>>>(pairs, imgs, desc8, norm, qlist, qmask, qcount, porder,
+                                                                      top2, slot1);
+            return hipGetLastError();
+        }
         if (pass2_variant() == 10 && qmask && top2) {   // subset-restricted pass 2
             static const int slots = resident_slots(sift_screen16_kernel<8, 4, 2, 64, true, true>, 256);
             if (slots > 0 && persist_screens())
@@ -2367,6 +2605,33 @@ hipError_t launch_assemble(const PairDev* pairs, int n_pairs, const ImgDev* imgs
     scan_offsets_kernel<<<1, 1024, 0, st>>>(counts, n_pairs, offsets);
     assemble_kernel<1><<<n_pairs, 1024, shmem, st>>>(pairs, imgs, out_idx, out_dist, distinct, min_count, counts, keep, offsets,
                                                      out, unsettled);
+    return hipGetLastError();
+}
+// The list path's settle + assembly (after the LISTS screen and subset kernels, and after the fp32
+// kernel of a mixed run): finish (ev_main is recorded behind it), one scan over every pair's count,
+// write.  recs: the run's pairs in any order, one workgroup each.
+hipError_t launch_finish_lists(const PairRec* recs, int n_pairs, const int32_t* qlist, const int32_t* qmask,
+                               const int32_t* qcount, unsigned long long* top2, const unsigned long long* slot1,
+                               int2* slow_list, int32_t* slow_count, const int8_t* desc8, const int32_t* norm,
+                               const int32_t* out_idx, const float* out_dist, double ratio, int distinct, int min_count,
+                               int max_nq, int max_nt, int64_t* counts, int32_t* keep, int64_t* offsets, DMatchDev* out,
+                               int32_t* unsettled, hipStream_t st, hipEvent_t ev_main) {
+    hipError_t e;
+    if (n_pairs == 0) {
+        (void)hipMemsetAsync(offsets, 0, sizeof(int64_t), st);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        return ev_main ? hipEventRecord(ev_main, st) : hipSuccess;
+    }
+    const size_t dup = distinct ? (size_t)2 * ((max_nt + 31) / 32) * 4 : 0;
+    const size_t shmem = (size_t)2 * ((max_nq + 31) / 32) * 4 + dup;
+    if (shmem > 150 * 1024) return hipErrorInvalidValue;
+    sift_finish_kernel<<<n_pairs, 1024, dup, st>>>(recs, qlist, qmask, qcount, top2, slot1, slow_list, slow_count, desc8, norm,
+                                                   out_idx, ratio, distinct, min_count, counts, keep, unsettled);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (ev_main && (e = hipEventRecord(ev_main, st)) != hipSuccess) return e;
+    scan_offsets_kernel<<<1, 1024, 0, st>>>(counts, n_pairs, offsets);
+    assemble_lists_kernel<<<n_pairs, 1024, shmem, st>>>(recs, qlist, qcount, top2, out_idx, out_dist, distinct, counts, offsets,
+                                                        out);
     return hipGetLastError();
 }
 

@@ -38,7 +38,12 @@ hipError_t launch_prep_hamming(const uint8_t*, int, int, int, uint8_t*, hipStrea
 hipError_t launch_sift_knn2(const WorkItem*, int, const PairDev*, const ImgDev*, const int8_t*, const int32_t*,
                             const int32_t*, const int32_t*, int32_t*, int32_t*, int, const int32_t*, WorkItem*,
                             int32_t*, int32_t*, float*, int2*, int32_t*, double, hipStream_t, hipEvent_t, int32_t*,
-                            unsigned long long*, unsigned long long*);
+                            unsigned long long*, unsigned long long*, bool);
+hipError_t launch_finish_lists(const PairRec*, int, const int32_t*, const int32_t*, const int32_t*, unsigned long long*,
+                               const unsigned long long*, int2*, int32_t*, const int8_t*, const int32_t*, const int32_t*,
+                               const float*, double, int, int, int, int, int64_t*, int32_t*, int64_t*, DMatchDev*, int32_t*,
+                               hipStream_t, hipEvent_t);
+bool persist_screens();
 hipError_t launch_sift_slow(const int2*, const int32_t*, const PairDev*, const ImgDev*, const int8_t*,
                             const int32_t*, int32_t*, float*, double, hipStream_t);
 hipError_t launch_sift_f32(const WorkItem*, int, const PairDev*, const ImgDev*, const float*, int32_t*, float*,
@@ -173,6 +178,7 @@ struct sfmx_matcher {
     DevView slow_count;              // int32: length of slow_list
     DevBuf qmask, top2;     // subset pass 2: per forwarded query its row-subset mask; per query the merged top-2 keys
     DevBuf porder, work2, work2_n;   // pair order (by train image) and the compacted pass-2 work list
+    DevBuf recs;                     // list path: one flat PairRec per pair, in porder order
     DevView unsettled;               // int32: pass-1 forwarded queries pass 2 never wrote (must stay 0)
     DevBuf prep_tab;                 // batched SIFT prep: one PrepImg per image
     PinnedBuf stage_prep, stage_run, stage_imgs, stage_flags; // pinned staging of the small uploads / flag readback
@@ -187,7 +193,8 @@ struct sfmx_matcher {
     bool plan_valid = false;
     int64_t plan_dense = 0;
     size_t plan_nwork = 0, plan_nwork32 = 0;
-    int plan_max_nt = 0;
+    int plan_max_nt = 0, plan_max_nq = 0;
+    bool plan_lists = false;         // the run settles and assembles from the forwarded lists (product SIFT path)
     bool has_run = false;
     // per run: start, main kernel end, run end, pass-1 end; a ring of EV_RING sets (r06) so the timing
     // of every run of a loop is readable afterwards (sfmx_matcher_timing_history) without a host sync
@@ -393,7 +400,12 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
     std::vector<int64_t> img_key(2 * (size_t)m->n_imgs);
     for (int i = 0; i < m->n_imgs; ++i) { img_key[2 * i] = m->imgs[i].rows; img_key[2 * i + 1] = m->imgs[i].integral; }
     const int nb_want = match_batches();
+    // List path: the product SIFT path (default screen, subset pass 2, one batch).  Every diagnostic
+    // variant and ORB keep the dense per-query arrays; fp32-fallback pairs of a list run do too, per pair.
+    const bool lists = m->norm == SFMX_NORM_L2 && variant_key == 0 && pass2_variant() == 10 && nb_want == 1 &&
+                       !persist_screens();
     const bool reuse = m->plan_valid && m->plan_variant == variant_key && m->plan_imgs == img_key && m->plan_nb == nb_want &&
+                       m->plan_lists == lists &&
                        m->plan_pairs.size() == 2 * (size_t)n_pairs &&
                        (n_pairs == 0 || std::memcmp(m->plan_pairs.data(), pairs, sizeof(int32_t) * 2 * n_pairs) == 0);
     int rc;
@@ -414,21 +426,28 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
         std::iota(order.begin(), order.end(), 0);
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pd[a].right < pd[b].right; });
         m->fp32_pairs = 0;
-        int max_nt = 0;
+        int max_nt = 0, max_nq = 0;
+        std::vector<PairRec> recs;
+        if (lists) recs.reserve(n_pairs);
         for (int p : order) {
             const ImgDev& L = m->imgs[pd[p].left];
             const ImgDev& R = m->imgs[pd[p].right];
             max_nt = std::max(max_nt, R.rows);
+            max_nq = std::max(max_nq, L.rows);
             const bool f32path = m->norm == SFMX_NORM_L2 && !(L.integral && R.integral);
             m->fp32_pairs += f32path;
+            if (lists) recs.push_back(PairRec{L.row0, R.row0, pd[p].dense_base, L.rows, R.rows, R.rows_pad, p, f32path ? 0 : 1, 0});
             const int bq = f32path ? 512 : (m->norm == SFMX_NORM_L2 ? sift_block_queries(sift_variant()) : 512);
             for (int q0 = 0; q0 < L.rows; q0 += bq) (f32path ? work32 : work).push_back(WorkItem{p, q0});
         }
         if ((rc = m->pairs_d.ensure(sizeof(PairDev) * std::max(n_pairs, 1)))) return rc;
         if ((rc = m->work_d.ensure(sizeof(WorkItem) * std::max<size_t>(work.size(), 1)))) return rc;
         if ((rc = m->work32_d.ensure(sizeof(WorkItem) * std::max<size_t>(work32.size(), 1)))) return rc;
-        if ((rc = m->dense_idx.ensure(sizeof(int32_t) * std::max<int64_t>(dense, 1)))) return rc;
-        if ((rc = m->dense_dist.ensure(sizeof(float) * std::max<int64_t>(dense, 1)))) return rc;
+        if (!lists || m->fp32_pairs) {   // the dense per-query results: not touched by a run of list pairs only
+            if ((rc = m->dense_idx.ensure(sizeof(int32_t) * std::max<int64_t>(dense, 1)))) return rc;
+            if ((rc = m->dense_dist.ensure(sizeof(float) * std::max<int64_t>(dense, 1)))) return rc;
+        }
+        if (lists && (rc = m->recs.ensure(sizeof(PairRec) * std::max(n_pairs, 1)))) return rc;
         if ((rc = m->slow_list.ensure(sizeof(int2) * std::max<int64_t>(dense, 1)))) return rc;
         if ((rc = m->qlist.ensure(sizeof(int32_t) * std::max<int64_t>(dense, 1)))) return rc;
         if (m->norm == SFMX_NORM_L2 || m->orb_fp4) {
@@ -444,19 +463,22 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
         if ((rc = m->keep.ensure(sizeof(int32_t) * std::max(n_pairs, 1)))) return rc;
         if ((rc = m->offsets.ensure(sizeof(int64_t) * (n_pairs + 1)))) return rc;
         if ((rc = m->out.ensure(sizeof(DMatchDev) * std::max<int64_t>(dense, 1)))) return rc;
-        // uploads from pinned staging: [pairs | order | work | work32], 256-B aligned parts
+        // uploads from pinned staging: [pairs | order | work | work32 | recs], 256-B aligned parts
         const size_t b_pd = align_up(sizeof(PairDev) * n_pairs, 256), b_or = align_up(sizeof(int32_t) * n_pairs, 256),
-                     b_w = align_up(sizeof(WorkItem) * work.size(), 256), b_w32 = sizeof(WorkItem) * work32.size();
-        if ((rc = m->stage_run.ensure(b_pd + b_or + b_w + b_w32))) return rc;
+                     b_w = align_up(sizeof(WorkItem) * work.size(), 256), b_w32 = align_up(sizeof(WorkItem) * work32.size(), 256),
+                     b_rc = sizeof(PairRec) * recs.size();
+        if ((rc = m->stage_run.ensure(b_pd + b_or + b_w + b_w32 + b_rc))) return rc;
         char* hs = m->stage_run.as<char>();
         std::memcpy(hs, pd.data(), sizeof(PairDev) * n_pairs);
         std::memcpy(hs + b_pd, order.data(), sizeof(int32_t) * n_pairs);
         std::memcpy(hs + b_pd + b_or, work.data(), sizeof(WorkItem) * work.size());
-        std::memcpy(hs + b_pd + b_or + b_w, work32.data(), b_w32);
+        std::memcpy(hs + b_pd + b_or + b_w, work32.data(), sizeof(WorkItem) * work32.size());
+        std::memcpy(hs + b_pd + b_or + b_w + b_w32, recs.data(), b_rc);
         if (n_pairs) HIPCHK(hipMemcpyAsync(m->pairs_d.p, hs, sizeof(PairDev) * n_pairs, hipMemcpyHostToDevice, st));
         if (n_pairs) HIPCHK(hipMemcpyAsync(m->porder.p, hs + b_pd, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, st));
         if (!work.empty()) HIPCHK(hipMemcpyAsync(m->work_d.p, hs + b_pd + b_or, sizeof(WorkItem) * work.size(), hipMemcpyHostToDevice, st));
-        if (!work32.empty()) HIPCHK(hipMemcpyAsync(m->work32_d.p, hs + b_pd + b_or + b_w, b_w32, hipMemcpyHostToDevice, st));
+        if (!work32.empty()) HIPCHK(hipMemcpyAsync(m->work32_d.p, hs + b_pd + b_or + b_w, sizeof(WorkItem) * work32.size(), hipMemcpyHostToDevice, st));
+        if (!recs.empty()) HIPCHK(hipMemcpyAsync(m->recs.p, hs + b_pd + b_or + b_w + b_w32, b_rc, hipMemcpyHostToDevice, st));
         if ((rc = m->stage_run.copied(st))) return rc;
         {   // batches of the overlapped two-pass path: whole pairs in `order`, about n_work / nb items each
             m->batches.clear();
@@ -487,6 +509,8 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
         m->plan_nwork = work.size();
         m->plan_nwork32 = work32.size();
         m->plan_max_nt = max_nt;
+        m->plan_max_nq = max_nq;
+        m->plan_lists = lists;
         m->plan_valid = true;
     }
     const int64_t dense = m->plan_dense;
@@ -548,10 +572,13 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
                                 m->work2.as<WorkItem>(), m->work2_n.as<int32_t>(), m->dense_idx.as<int32_t>(),
                                 m->dense_dist.as<float>(), m->slow_list.as<int2>(), m->slow_count.as<int32_t>(), ratio, st,
                                 m->ev[3], m->qmask.as<int32_t>(), m->top2.as<unsigned long long>(),
-                                m->out.as<unsigned long long>()));   // pass 2's second slot: `out` is idle until assembly
-        HIPCHK(hipEventRecord(m->ev[1], st));
-        HIPCHK(launch_sift_slow(m->slow_list.as<int2>(), m->slow_count.as<int32_t>(), P, I, m->desc8.as<int8_t>(),
-                                m->normv.as<int32_t>(), m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), ratio, st));
+                                m->out.as<unsigned long long>(),   // pass 2's second slot: `out` is idle until assembly
+                                m->plan_lists));
+        if (!m->plan_lists) {
+            HIPCHK(hipEventRecord(m->ev[1], st));
+            HIPCHK(launch_sift_slow(m->slow_list.as<int2>(), m->slow_count.as<int32_t>(), P, I, m->desc8.as<int8_t>(),
+                                    m->normv.as<int32_t>(), m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), ratio, st));
+        }
         if (n_work32)
             HIPCHK(launch_sift_f32(m->work32_d.as<WorkItem>(), (int)n_work32, P, I, m->f32.as<float>(),
                                    m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), ratio, st));
@@ -568,9 +595,18 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
         HIPCHK(hipEventRecord(m->ev[1], st));
     }
     const int max_nt = m->plan_max_nt;
-    HIPCHK(launch_assemble(P, n_pairs, I, m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), distinct ? 1 : 0,
-                           min_count, max_nt, m->counts.as<int64_t>(), m->keep.as<int32_t>(),
-                           m->offsets.as<int64_t>(), m->out.as<DMatchDev>(), m->unsettled.as<int32_t>(), st));
+    if (m->plan_lists)   // settle + count (ev[1] behind it), scan, write: the writer of `out` runs after slot1's last reader
+        HIPCHK(launch_finish_lists(m->recs.as<PairRec>(), n_pairs, m->qlist.as<int32_t>(), m->qmask.as<int32_t>(),
+                                   m->qcount.as<int32_t>(), m->top2.as<unsigned long long>(),
+                                   m->out.as<unsigned long long>(), m->slow_list.as<int2>(), m->slow_count.as<int32_t>(),
+                                   m->desc8.as<int8_t>(), m->normv.as<int32_t>(), m->dense_idx.as<int32_t>(),
+                                   m->dense_dist.as<float>(), ratio, distinct ? 1 : 0, min_count, m->plan_max_nq, max_nt,
+                                   m->counts.as<int64_t>(), m->keep.as<int32_t>(), m->offsets.as<int64_t>(),
+                                   m->out.as<DMatchDev>(), m->unsettled.as<int32_t>(), st, m->ev[1]));
+    else
+        HIPCHK(launch_assemble(P, n_pairs, I, m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), distinct ? 1 : 0,
+                               min_count, max_nt, m->counts.as<int64_t>(), m->keep.as<int32_t>(),
+                               m->offsets.as<int64_t>(), m->out.as<DMatchDev>(), m->unsettled.as<int32_t>(), st));
     HIPCHK(hipEventRecord(m->ev[2], st));
     m->ev_recorded = true;
     m->n_pairs = n_pairs;
@@ -732,7 +768,7 @@ int sfmx_matcher_destroy(sfmx_matcher* m) {
         m->hflags = nullptr;
         DevBuf* bufs[] = {&m->raw, &m->desc8, &m->normv, &m->keyc, &m->keyc2, &m->qlist, &m->qcount, &m->porder, &m->work2, &m->work2_n, &m->f32, &m->flags, &m->imgs_d, &m->pairs_d, &m->prep_tab,
                           &m->work_d, &m->work32_d, &m->dense_idx, &m->dense_dist, &m->slow_list,
-                          &m->counts, &m->keep, &m->offsets, &m->out};
+                          &m->counts, &m->keep, &m->offsets, &m->out, &m->qmask, &m->top2, &m->recs};
         for (DevBuf* b : bufs) b->release();
         for (auto& set : m->evr)
             for (auto& e : set) if (e) (void)hipEventDestroy(e);
