@@ -1,0 +1,610 @@
+// SPDX-License-Identifier: MIT
+// sfmx triangulation of shot matches for gfx950: SfM::triangulateMatch (sfm/SfM.cpp:383-451) for every
+// pair of a match graph in one call (include/sfmx_triangulate.h; DESIGN.md has the algorithm).
+//
+// Three kernels over the packed match list, one thread per match, all pairs in one launch:
+//   1. tri_solve_kernel    undistortPoints -> the 4x4 DLT system -> its null vector by the one-sided Jacobi
+//                          of OpenCV's JacobiSVDImpl_ -> convertPointsFromHomogeneous -> projectPoints into
+//                          both views -> reprojection errors and the keep flag.  Writes float X, Y, Z and
+//                          the two keypoints of kept matches, one keep mask per wave, one count per block.
+//   2. tri_scan_kernel     exclusive scan of the block counts (one block, looped, any number of blocks) and
+//                          the point offsets at the pair boundaries.
+//   3. tri_compact_kernel  stable compaction by mask popcount prefix into the caller's arrays.
+// All arithmetic is fp64 (float where OpenCV's arrays are float), one correctly rounded IEEE operation per
+// step in the order of tests/tri_ref.py; the file is compiled with -ffp-contract=off and calls no libm
+// function but sqrt.  At, V and W of the Jacobi live in registers: every loop over them is fully unrolled
+// and the row sort is compare / select, so nothing is indexed dynamically (no scratch).
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <climits>
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "../../include/sfmx_triangulate.h"
+#include "match_common.hpp"
+
+namespace sfmx {
+namespace tri {
+
+struct ShotT {            // one shot: its pose, its camera, its keypoints
+    double P[12];         // 3x4 [R|t] row-major
+    double fx, fy, cx, cy, ifx, ify, k1, k2, p1, p2, k3;
+    const float2* kp;
+    int32_t nkp, _pad;
+};
+
+constexpr int BLOCK = 256;
+constexpr int MAX_SWEEPS = 30;
+
+// largest p in [lo, hi] with off[p] <= g: the pair whose list holds match g (empty pairs are passed over)
+__device__ __forceinline__ int search_pair(int64_t g, const int64_t* __restrict__ off, int lo, int hi) {
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= g) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// The pair of match g (g < n).  One search per wave for its first match; `uniform` tells whether the whole
+// wave lies inside that pair, else every lane searches on from there.
+__device__ __forceinline__ int pair_of(int64_t g, int64_t n, const int64_t* __restrict__ off, int n_pairs, bool& uniform) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t g0 = min((int64_t)blockIdx.x * BLOCK + wave * 64, n - 1);
+    const int p0 = search_pair(g0, off, 0, n_pairs - 1);
+    uniform = min(g0 + 63, n - 1) < off[p0 + 1];
+    return uniform ? p0 : search_pair(g, off, p0, n_pairs - 1);
+}
+
+// cv::undistortPoints, TermCriteria(COUNT, 5); the result is rounded to float
+__device__ __forceinline__ void undistort(const float2 pt, const ShotT* __restrict__ S, float& ox, float& oy) {
+    const double k1 = S->k1, k2 = S->k2, p1 = S->p1, p2 = S->p2, k3 = S->k3;
+    double x = ((double)pt.x - S->cx) * S->ifx;
+    double y = ((double)pt.y - S->cy) * S->ify;
+    const double x0 = x, y0 = y;
+#pragma unroll 1
+    for (int it = 0; it < 5; ++it) {
+        const double r2 = x * x + y * y;
+        const double icdist = 1.0 / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2);
+        if (icdist < 0) { x = x0; y = y0; break; }
+        const double dX = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
+        const double dY = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y;
+        x = (x0 - dX) * icdist;
+        y = (y0 - dY) * icdist;
+    }
+    ox = (float)x;
+    oy = (float)y;
+}
+
+// two rows of the DLT system of one view, stored transposed: At[k][row] = A[row][k]
+__device__ __forceinline__ void dlt_rows(const ShotT* __restrict__ S, float xf, float yf, int row, double (&At)[4][4]) {
+    const double x = (double)xf, y = (double)yf;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double p0 = S->P[k], p1 = S->P[4 + k], p2 = S->P[8 + k];
+        if (row == 0) { At[k][0] = x * p2 - p0; At[k][1] = y * p2 - p1; }
+        else          { At[k][2] = x * p2 - p0; At[k][3] = y * p2 - p1; }
+    }
+}
+
+__device__ __forceinline__ double sum4(double a, double b, double c, double d) { return ((a + b) + c) + d; }
+
+// one Jacobi rotation of rows I, J (JacobiSVDImpl_); false when the pair is already orthogonal
+template <int I, int J>
+__device__ __forceinline__ bool rotate(double (&At)[4][4], double (&V)[4][4], double (&W)[4]) {
+    const double eps = 10.0 * 2.220446049250313e-16;   // 10 * DBL_EPSILON
+    double p = sum4(At[I][0] * At[J][0], At[I][1] * At[J][1], At[I][2] * At[J][2], At[I][3] * At[J][3]);
+    if (fabs(p) <= eps * sqrt(W[I] * W[J])) return false;
+    p = 2.0 * p;
+    const double beta = W[I] - W[J];
+    const double gamma = sqrt(p * p + beta * beta);   // OpenCV: hypot(p, beta)
+    double c, s;
+    if (beta < 0) {
+        s = sqrt(((gamma - beta) * 0.5) / gamma);
+        c = p / (gamma * s * 2.0);
+    } else {
+        c = sqrt((gamma + beta) / (gamma * 2.0));
+        s = p / (gamma * c * 2.0);
+    }
+    double t0[4], t1[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        t0[k] = c * At[I][k] + s * At[J][k];
+        t1[k] = c * At[J][k] - s * At[I][k];
+        At[I][k] = t0[k];
+        At[J][k] = t1[k];
+    }
+    W[I] = sum4(t0[0] * t0[0], t0[1] * t0[1], t0[2] * t0[2], t0[3] * t0[3]);
+    W[J] = sum4(t1[0] * t1[0], t1[1] * t1[1], t1[2] * t1[2], t1[3] * t1[3]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double v0 = c * V[I][k] + s * V[J][k];
+        const double v1 = c * V[J][k] - s * V[I][k];
+        V[I][k] = v0;
+        V[J][k] = v1;
+    }
+    return true;
+}
+
+// the right singular vector of the smallest singular value: row 3 of V after the descending sort, as float
+__device__ __forceinline__ void jacobi_null(double (&At)[4][4], float (&h)[4]) {
+    double V[4][4], W[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) V[i][k] = i == k ? 1.0 : 0.0;
+        W[i] = sum4(At[i][0] * At[i][0], At[i][1] * At[i][1], At[i][2] * At[i][2], At[i][3] * At[i][3]);
+    }
+#pragma unroll 1
+    for (int sweep = 0; sweep < MAX_SWEEPS; ++sweep) {
+        bool changed = rotate<0, 1>(At, V, W);
+        changed |= rotate<0, 2>(At, V, W);
+        changed |= rotate<0, 3>(At, V, W);
+        changed |= rotate<1, 2>(At, V, W);
+        changed |= rotate<1, 3>(At, V, W);
+        changed |= rotate<2, 3>(At, V, W);
+        if (!changed) break;
+    }
+    int idx[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        W[i] = sqrt(sum4(At[i][0] * At[i][0], At[i][1] * At[i][1], At[i][2] * At[i][2], At[i][3] * At[i][3]));
+        idx[i] = i;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {   // selection sort, descending; the rows follow through idx
+        int j = i;
+        double wj = W[i];
+#pragma unroll
+        for (int k = i + 1; k < 4; ++k) {
+            const bool lt = wj < W[k];
+            j = lt ? k : j;
+            wj = lt ? W[k] : wj;
+        }
+#pragma unroll
+        for (int m = i + 1; m < 4; ++m) {
+            const bool sw = j == m;
+            const double wi = W[i], wm = W[m];
+            const int ii = idx[i], im = idx[m];
+            W[i] = sw ? wm : wi;
+            W[m] = sw ? wi : wm;
+            idx[i] = sw ? im : ii;
+            idx[m] = sw ? ii : im;
+        }
+    }
+    const int r = idx[3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) h[k] = (float)(r == 0 ? V[0][k] : (r == 1 ? V[1][k] : (r == 2 ? V[2][k] : V[3][k])));
+}
+
+// A NaN result leaves as the canonical quiet NaN: IEEE 754 leaves the sign and payload of a NaN open, and
+// x86 and gfx950 produce different ones.  On the bit patterns: the compiler folds `v != v ? NaN : v` to v.
+__device__ __forceinline__ float canon(float v) {
+    const uint32_t b = __float_as_uint(v);
+    return __uint_as_float((b & 0x7FFFFFFFu) > 0x7F800000u ? 0x7FC00000u : b);
+}
+__device__ __forceinline__ double canon(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return __longlong_as_double((long long)((b & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull ? 0x7FF8000000000000ull : b));
+}
+
+// cv::projectPoints with R, t of the pose, then the reprojection error against the keypoint
+__device__ __forceinline__ double reproject_error(const ShotT* __restrict__ S, float Xf, float Yf, float Zf, const float2 pt) {
+    const double X = (double)Xf, Y = (double)Yf, Z = (double)Zf;
+    double x = S->P[0] * X + S->P[1] * Y + S->P[2] * Z + S->P[3];
+    double y = S->P[4] * X + S->P[5] * Y + S->P[6] * Z + S->P[7];
+    double z = S->P[8] * X + S->P[9] * Y + S->P[10] * Z + S->P[11];
+    z = z != 0 ? 1.0 / z : 1.0;
+    x = x * z;
+    y = y * z;
+    const double r2 = x * x + y * y;
+    const double r4 = r2 * r2;
+    const double r6 = r4 * r2;
+    const double a1 = 2.0 * x * y;
+    const double a2 = r2 + 2.0 * x * x;
+    const double a3 = r2 + 2.0 * y * y;
+    const double cdist = 1.0 + S->k1 * r2 + S->k2 * r4 + S->k3 * r6;
+    const double xd = x * cdist + S->p1 * a1 + S->p2 * a2;
+    const double yd = y * cdist + S->p1 * a3 + S->p2 * a1;
+    const float u = (float)(xd * S->fx + S->cx);
+    const float v = (float)(yd * S->fy + S->cy);
+    const float du = u - pt.x, dv = v - pt.y;
+    const double e = sqrt((double)du * (double)du + (double)dv * (double)dv);
+    return canon(e);
+}
+
+// steps a and b up to the DLT system (transposed)
+__device__ __forceinline__ void build_system(const ShotT* __restrict__ SL, const ShotT* __restrict__ SR, const float2 l,
+                                             const float2 r, double (&At)[4][4]) {
+    float xl, yl, xr, yr;
+    undistort(l, SL, xl, yl);
+    undistort(r, SR, xr, yr);
+    dlt_rows(SL, xl, yl, 0, At);
+    dlt_rows(SR, xr, yr, 1, At);
+}
+
+__global__ __launch_bounds__(BLOCK)
+void tri_solve_kernel(const ShotT* __restrict__ shots, const int32_t* __restrict__ pairs, int n_pairs,
+                      const DMatchDev* __restrict__ matches, const int64_t* __restrict__ off, int64_t n, double max_err,
+                      float4* __restrict__ sxyz, float4* __restrict__ slr, unsigned long long* __restrict__ keepmask,
+                      int32_t* __restrict__ block_count, double* __restrict__ out_err, int64_t* __restrict__ res) {
+    __shared__ int s_cnt[BLOCK / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t g = (int64_t)blockIdx.x * BLOCK + tid;
+    const bool in = g < n;
+    const int64_t gc = in ? g : n - 1;
+    bool uniform;
+    const int p = pair_of(gc, n, off, n_pairs, uniform);
+    // The two table rows of the pair: every lane of a wave inside one pair reads the same addresses, which the
+    // vector memory path serves as one broadcast cache line per load (duplicating the body behind wave-uniform
+    // pointers does not survive the compiler: it merges the two copies back into one with a selected pointer).
+    const ShotT* SL = shots + pairs[2 * p];
+    const ShotT* SR = shots + pairs[2 * p + 1];
+    const DMatchDev d = matches[gc];
+    const bool valid = in && d.queryIdx >= 0 && d.queryIdx < SL->nkp && d.trainIdx >= 0 && d.trainIdx < SR->nkp;
+    if (in && !valid) res[1] = 1;   // a match index outside its image's keypoints: the call fails
+    bool keep = false;
+    if (valid) {
+        const float2 l = SL->kp[d.queryIdx], r = SR->kp[d.trainIdx];
+        double At[4][4];
+        build_system(SL, SR, l, r, At);
+        float h[4];
+        jacobi_null(At, h);
+        const float scale = h[3] != 0.f ? 1.f / h[3] : 1.f;   // convertPointsFromHomogeneous, in float
+        const float X = h[0] * scale, Y = h[1] * scale, Z = h[2] * scale;
+        // the poses and cameras are read again here, not held in ~90 registers across the Jacobi sweeps
+        // (116 instead of 192 VGPRs): the empty asm keeps the compiler from merging the two reads
+        const ShotT *PL = SL, *PR = SR;
+        asm volatile("" : "+v"(PL), "+v"(PR));
+        const double eL = reproject_error(PL, X, Y, Z, l);
+        const double eR = reproject_error(PR, X, Y, Z, r);
+        keep = !(eL > max_err || eR > max_err);   // a NaN error keeps the point (SfM.cpp:434)
+        if (out_err) {
+            out_err[2 * g] = eL;
+            out_err[2 * g + 1] = eR;
+        }
+        if (keep) {
+            sxyz[g] = make_float4(canon(X), canon(Y), canon(Z), 0.f);
+            slr[g] = make_float4(l.x, l.y, r.x, r.y);
+        }
+    }
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) {
+        keepmask[g >> 6] = mask;
+        s_cnt[wave] = __popcll(mask);
+    }
+    __syncthreads();
+    if (tid == 0) block_count[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// One block: block_off = exclusive scan of block_count (chunks of 1024 with a carry), then the number of
+// points before every pair boundary and the total.
+__global__ __launch_bounds__(1024)
+void tri_scan_kernel(const int32_t* __restrict__ block_count, int64_t n_blocks, int64_t* __restrict__ block_off,
+                     const unsigned long long* __restrict__ keepmask, const int64_t* __restrict__ off, int n_pairs,
+                     int64_t n, int64_t* __restrict__ out_point_offsets, int64_t* __restrict__ res) {
+    __shared__ long long s_wave[16];
+    __shared__ long long s_carry;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) s_carry = 0;
+    __syncthreads();
+    for (int64_t base = 0; base < n_blocks; base += 1024) {
+        const int64_t i = base + tid;
+        const long long v = i < n_blocks ? block_count[i] : 0;
+        long long x = v;
+#pragma unroll
+        for (int dlt = 1; dlt < 64; dlt <<= 1) {
+            const long long t = __shfl_up(x, dlt);
+            if (lane >= dlt) x += t;
+        }
+        if (lane == 63) s_wave[wave] = x;
+        __syncthreads();
+        long long woff = 0;
+        for (int w = 0; w < wave; ++w) woff += s_wave[w];
+        const long long carry = s_carry;
+        if (i < n_blocks) block_off[i] = carry + woff + x - v;
+        __syncthreads();
+        if (tid == 1023) s_carry = carry + woff + x;
+        __syncthreads();
+    }
+    const long long total = s_carry;
+    for (int p = tid; p <= n_pairs; p += 1024) {
+        const int64_t g = min(max(off[p], (int64_t)0), n);
+        long long v = total;
+        if (g < n) {
+            const int64_t blk = g >> 8, wq = g >> 6;
+            v = block_off[blk];
+            for (int64_t w = blk * 4; w < wq; ++w) v += __popcll(keepmask[w]);
+            v += __popcll(keepmask[wq] & ((1ull << (g & 63)) - 1ull));
+        }
+        out_point_offsets[p] = v;
+    }
+    if (tid == 0) res[0] = total;
+}
+
+__global__ __launch_bounds__(BLOCK)
+void tri_compact_kernel(const int32_t* __restrict__ pairs, int n_pairs, const int64_t* __restrict__ off, int64_t n,
+                        const float4* __restrict__ sxyz, const float4* __restrict__ slr,
+                        const unsigned long long* __restrict__ keepmask, const int64_t* __restrict__ block_off,
+                        double* __restrict__ out_xyz, int64_t* __restrict__ out_match,
+                        int32_t* __restrict__ out_origin_shot, double* __restrict__ out_origin_xy) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t g = (int64_t)blockIdx.x * BLOCK + tid;
+    const int64_t gc = g < n ? g : n - 1;
+    bool uniform;
+    const int p = pair_of(gc, n, off, n_pairs, uniform);
+    if (g >= n) return;
+    const unsigned long long mask = keepmask[g >> 6];
+    if (!((mask >> lane) & 1ull)) return;
+    int64_t pos = block_off[blockIdx.x];
+    for (int w = 0; w < wave; ++w) pos += __popcll(keepmask[(int64_t)blockIdx.x * 4 + w]);
+    pos += __popcll(mask & ((1ull << lane) - 1ull));
+    const float4 a = sxyz[g], b = slr[g];
+    out_xyz[3 * pos] = (double)a.x;
+    out_xyz[3 * pos + 1] = (double)a.y;
+    out_xyz[3 * pos + 2] = (double)a.z;
+    out_match[pos] = g;
+    out_origin_shot[2 * pos] = pairs[2 * p];
+    out_origin_shot[2 * pos + 1] = pairs[2 * p + 1];
+    out_origin_xy[4 * pos] = (double)b.x;
+    out_origin_xy[4 * pos + 1] = (double)b.y;
+    out_origin_xy[4 * pos + 2] = (double)b.z;
+    out_origin_xy[4 * pos + 3] = (double)b.w;
+}
+
+thread_local float g_last_ms = -1.f;
+
+// Per device, kept between calls (as homography.hip): the device check's result, one device block for the
+// call's tables and scratch (regrown with headroom), pinned staging for the small uploads and the result
+// words, two timing events.
+struct Slot {
+    bool checked = false;
+    char* dev = nullptr;
+    size_t dev_cap = 0;
+    char* pin = nullptr;
+    size_t pin_cap = 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    std::mutex mu;   // one call per device at a time
+};
+Slot g_slot[64];
+size_t r256(size_t b) { return (std::max<size_t>(b, 1) + 255) & ~(size_t)255; }
+
+}  // namespace tri
+}  // namespace sfmx
+
+using namespace sfmx;
+using namespace sfmx::tri;
+
+#define TCHK(expr) do { if ((expr) != hipSuccess) { rc = SFMX_EDEVICE; goto done; } } while (0)
+
+extern "C" {
+
+float sfmx_triangulate_last_kernel_ms(void) { return g_last_ms; }
+
+int sfmx_triangulate_matches(const sfmx_point2f* const* keypoints, const int32_t* n_keypoints, int32_t n_shots,
+                             const sfmx_tri_camera* cameras, int32_t n_cameras, const int32_t* shot_camera,
+                             const double* shot_pose, const int32_t* pairs, int32_t n_pairs,
+                             const sfmx_dmatch* matches, const int64_t* pair_offsets, double max_reprojection_error,
+                             int32_t inputs_on_device, int32_t device, void* stream, int64_t* out_point_offsets,
+                             double* out_xyz, int64_t* out_match, int32_t* out_origin_shot, double* out_origin_xy,
+                             double* out_err, int64_t* out_n_points) {
+    if (n_shots < 0 || n_cameras < 0 || n_pairs < 0) { set_last_error("negative count"); return SFMX_EINVAL; }
+    if (!out_n_points || !out_point_offsets || !pair_offsets || (n_pairs && !pairs) ||
+        (n_shots && (!keypoints || !n_keypoints || !shot_camera || !shot_pose)) || (n_cameras && !cameras)) {
+        set_last_error("null argument");
+        return SFMX_EINVAL;
+    }
+    *out_n_points = 0;
+    for (int c = 0; c < n_cameras; ++c)
+        if (cameras[c].K[0] == 0.0 || cameras[c].K[4] == 0.0) { set_last_error("camera with zero focal length"); return SFMX_EINVAL; }
+    for (int s = 0; s < n_shots; ++s) {
+        if (shot_camera[s] < 0 || shot_camera[s] >= n_cameras) { set_last_error("shot camera index out of range"); return SFMX_EINVAL; }
+        if (n_keypoints[s] < 0) { set_last_error("negative keypoint count"); return SFMX_EINVAL; }
+    }
+    for (int p = 0; p < n_pairs; ++p)
+        if (pairs[2 * p] < 0 || pairs[2 * p] >= n_shots || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= n_shots) {
+            set_last_error("pair shot index out of range");
+            return SFMX_EINVAL;
+        }
+    const hipStream_t st = (hipStream_t)stream;
+    Slot* S = nullptr;
+    int prev = -1;
+    if (inputs_on_device || pair_offsets[n_pairs] != 0) {   // anything but an empty host call needs the device
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_last_error("no HIP device visible"); return SFMX_EDEVICE; }
+        if (device < 0 || device >= ndev || device >= 64) { set_last_error("device index out of range"); return SFMX_EINVAL; }
+        S = &g_slot[device];
+    }
+    std::unique_lock<std::mutex> lock;
+    if (S) {
+        lock = std::unique_lock<std::mutex>(S->mu);
+        if (!S->checked) {
+            hipDeviceProp_t prop;
+            if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+                set_last_error("sfmx kernels are built for gfx950 only");
+                return SFMX_EDEVICE;
+            }
+            S->checked = true;
+        }
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(device);
+    }
+    int rc = SFMX_OK;
+    {
+        // the pair offsets on the host: they size the launch
+        std::vector<int64_t> hoff(n_pairs + 1);
+        int64_t n = 0, n_blocks = 0, nk = 0;
+        if (inputs_on_device) {
+            TCHK(hipMemcpyAsync(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
+            TCHK(hipStreamSynchronize(st));
+        } else {
+            std::memcpy(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1));
+        }
+        if (hoff[0] != 0) { set_last_error("pair offsets do not start at 0"); rc = SFMX_EINVAL; goto done; }
+        for (int p = 0; p < n_pairs; ++p)
+            if (hoff[p + 1] < hoff[p]) { set_last_error("pair offsets not ascending"); rc = SFMX_EINVAL; goto done; }
+        n = hoff[n_pairs];
+        if (n == 0) {   // no match: nothing is launched
+            if (inputs_on_device) {
+                TCHK(hipMemsetAsync(out_point_offsets, 0, sizeof(int64_t) * (n_pairs + 1), st));
+                TCHK(hipStreamSynchronize(st));
+            } else {
+                std::memset(out_point_offsets, 0, sizeof(int64_t) * (n_pairs + 1));
+            }
+            g_last_ms = 0.f;
+            goto done;
+        }
+        if (!matches || !out_xyz || !out_match || !out_origin_shot || !out_origin_xy) {
+            set_last_error("null argument");
+            rc = SFMX_EINVAL;
+            goto done;
+        }
+        n_blocks = (n + BLOCK - 1) / BLOCK;
+        if (n_blocks > INT32_MAX) { set_last_error("too many matches"); rc = SFMX_EINVAL; goto done; }
+        if (!inputs_on_device) {
+            for (int p = 0; p < n_pairs; ++p) {
+                const int L = pairs[2 * p], R = pairs[2 * p + 1];
+                for (int64_t i = hoff[p]; i < hoff[p + 1]; ++i)
+                    if (matches[i].queryIdx < 0 || matches[i].queryIdx >= n_keypoints[L] || matches[i].trainIdx < 0 ||
+                        matches[i].trainIdx >= n_keypoints[R]) {
+                        set_last_error("match index outside its image's keypoints");
+                        rc = SFMX_EINVAL;
+                        goto done;
+                    }
+            }
+            for (int i = 0; i < n_shots; ++i) nk += n_keypoints[i];
+        }
+        {
+            // device block: [shot table | pairs | result words | block counts | block offsets | keep masks |
+            // xyz scratch | keypoint scratch | (host inputs: keypoints, matches, offsets, every output)]
+            const bool H = !inputs_on_device;
+            const size_t b_sh = r256(sizeof(ShotT) * n_shots), b_pr = r256(sizeof(int32_t) * 2 * n_pairs), b_res = 256,
+                         b_bc = r256(sizeof(int32_t) * n_blocks), b_bo = r256(sizeof(int64_t) * n_blocks),
+                         b_km = r256(sizeof(unsigned long long) * n_blocks * (BLOCK / 64)),
+                         b_s1 = r256(sizeof(float4) * n), b_s2 = r256(sizeof(float4) * n);
+            const size_t b_kd = H ? r256(sizeof(float2) * nk) : 0, b_md = H ? r256(sizeof(sfmx_dmatch) * n) : 0,
+                         b_od = H ? r256(sizeof(int64_t) * (n_pairs + 1)) : 0,
+                         b_po = H ? r256(sizeof(int64_t) * (n_pairs + 1)) : 0, b_ox = H ? r256(sizeof(double) * 3 * n) : 0,
+                         b_om = H ? r256(sizeof(int64_t) * n) : 0, b_os = H ? r256(sizeof(int32_t) * 2 * n) : 0,
+                         b_oy = H ? r256(sizeof(double) * 4 * n) : 0, b_oe = H && out_err ? r256(sizeof(double) * 2 * n) : 0;
+            const size_t need = b_sh + b_pr + b_res + b_bc + b_bo + b_km + b_s1 + b_s2 + b_kd + b_md + b_od + b_po + b_ox +
+                                b_om + b_os + b_oy + b_oe;
+            if (S->dev_cap < need) {
+                if (S->dev) (void)hipFree(S->dev);
+                S->dev = nullptr;
+                S->dev_cap = 0;
+                if (hipMalloc(reinterpret_cast<void**>(&S->dev), need + need / 4) != hipSuccess) {
+                    S->dev = nullptr;
+                    (void)hipGetLastError();
+                    rc = SFMX_ENOMEM;
+                    goto done;
+                }
+                S->dev_cap = need + need / 4;
+            }
+            const size_t need_pin = b_sh + b_pr + b_res;
+            if (S->pin_cap < need_pin) {
+                if (S->pin) (void)hipHostFree(S->pin);
+                S->pin = nullptr;
+                S->pin_cap = 0;
+                if (hipHostMalloc(reinterpret_cast<void**>(&S->pin), need_pin + need_pin / 4, hipHostMallocDefault) != hipSuccess) {
+                    S->pin = nullptr;
+                    rc = SFMX_ENOMEM;
+                    goto done;
+                }
+                S->pin_cap = need_pin + need_pin / 4;
+            }
+            if (!S->e0 && (hipEventCreate(&S->e0) != hipSuccess || hipEventCreate(&S->e1) != hipSuccess)) { rc = SFMX_EDEVICE; goto done; }
+            char* d = S->dev;
+            ShotT* shd = reinterpret_cast<ShotT*>(d);                                  d += b_sh;
+            int32_t* prd = reinterpret_cast<int32_t*>(d);                              d += b_pr;
+            int64_t* resd = reinterpret_cast<int64_t*>(d);                             d += b_res;
+            int32_t* bcd = reinterpret_cast<int32_t*>(d);                              d += b_bc;
+            int64_t* bod = reinterpret_cast<int64_t*>(d);                              d += b_bo;
+            unsigned long long* kmd = reinterpret_cast<unsigned long long*>(d);        d += b_km;
+            float4* s1 = reinterpret_cast<float4*>(d);                                 d += b_s1;
+            float4* s2 = reinterpret_cast<float4*>(d);                                 d += b_s2;
+            float2* kd = reinterpret_cast<float2*>(d);                                 d += b_kd;
+            sfmx_dmatch* md = reinterpret_cast<sfmx_dmatch*>(d);                       d += b_md;
+            int64_t* od = reinterpret_cast<int64_t*>(d);                               d += b_od;
+            int64_t* pod = reinterpret_cast<int64_t*>(d);                              d += b_po;
+            double* oxd = reinterpret_cast<double*>(d);                                d += b_ox;
+            int64_t* omd = reinterpret_cast<int64_t*>(d);                              d += b_om;
+            int32_t* osd = reinterpret_cast<int32_t*>(d);                              d += b_os;
+            double* oyd = reinterpret_cast<double*>(d);                                d += b_oy;
+            double* oed = reinterpret_cast<double*>(d);
+            // shot table: pose, camera and keypoint pointer of every shot
+            ShotT* hs = reinterpret_cast<ShotT*>(S->pin);
+            int64_t o = 0;
+            for (int i = 0; i < n_shots; ++i) {
+                const sfmx_tri_camera& c = cameras[shot_camera[i]];
+                ShotT& t = hs[i];
+                std::memcpy(t.P, shot_pose + 12 * i, sizeof(double) * 12);
+                t.fx = c.K[0]; t.fy = c.K[4]; t.cx = c.K[2]; t.cy = c.K[5];
+                t.ifx = 1.0 / c.K[0]; t.ify = 1.0 / c.K[4];
+                t.k1 = c.dist[0]; t.k2 = c.dist[1]; t.p1 = c.dist[2]; t.p2 = c.dist[3]; t.k3 = c.dist[4];
+                t.nkp = n_keypoints[i];
+                t._pad = 0;
+                if (H) {
+                    if (n_keypoints[i]) TCHK(hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st));
+                    t.kp = kd + o;
+                    o += n_keypoints[i];
+                } else {
+                    t.kp = reinterpret_cast<const float2*>(keypoints[i]);
+                }
+            }
+            std::memcpy(S->pin + b_sh, pairs, sizeof(int32_t) * 2 * n_pairs);
+            int64_t* hres = reinterpret_cast<int64_t*>(S->pin + b_sh + b_pr);
+            hres[0] = hres[1] = 0;
+            TCHK(hipMemcpyAsync(S->dev, S->pin, b_sh + b_pr + b_res, hipMemcpyHostToDevice, st));   // tables, result words = 0
+            const DMatchDev* dm = reinterpret_cast<const DMatchDev*>(matches);
+            const int64_t* doff = pair_offsets;
+            int64_t* dpo = out_point_offsets;
+            double *dox = out_xyz, *doy = out_origin_xy, *doe = out_err;
+            int64_t* dom = out_match;
+            int32_t* dos = out_origin_shot;
+            if (H) {
+                TCHK(hipMemcpyAsync(md, matches, sizeof(sfmx_dmatch) * n, hipMemcpyHostToDevice, st));
+                TCHK(hipMemcpyAsync(od, pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyHostToDevice, st));
+                dm = reinterpret_cast<const DMatchDev*>(md);
+                doff = od; dpo = pod; dox = oxd; dom = omd; dos = osd; doy = oyd;
+                doe = out_err ? oed : nullptr;
+            }
+            (void)hipEventRecord(S->e0, st);
+            tri_solve_kernel<<<(unsigned)n_blocks, BLOCK, 0, st>>>(shd, prd, n_pairs, dm, doff, n, max_reprojection_error, s1, s2,
+                                                                   kmd, bcd, doe, resd);
+            tri_scan_kernel<<<1, 1024, 0, st>>>(bcd, n_blocks, bod, kmd, doff, n_pairs, n, dpo, resd);
+            tri_compact_kernel<<<(unsigned)n_blocks, BLOCK, 0, st>>>(prd, n_pairs, doff, n, s1, s2, kmd, bod, dox, dom, dos, doy);
+            (void)hipEventRecord(S->e1, st);
+            TCHK(hipGetLastError());
+            TCHK(hipMemcpyAsync(hres, resd, sizeof(int64_t) * 2, hipMemcpyDeviceToHost, st));   // total and the index flag
+            TCHK(hipStreamSynchronize(st));
+            if (hres[1] != 0) { set_last_error("match index outside its image's keypoints"); rc = SFMX_EINVAL; goto done; }
+            const int64_t total = hres[0];
+            if (total < 0 || total > n) { set_last_error("point count self check failed"); rc = SFMX_EINTERNAL; goto done; }
+            if (H) {
+                TCHK(hipMemcpyAsync(out_point_offsets, pod, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
+                if (total) {
+                    TCHK(hipMemcpyAsync(out_xyz, oxd, sizeof(double) * 3 * total, hipMemcpyDeviceToHost, st));
+                    TCHK(hipMemcpyAsync(out_match, omd, sizeof(int64_t) * total, hipMemcpyDeviceToHost, st));
+                    TCHK(hipMemcpyAsync(out_origin_shot, osd, sizeof(int32_t) * 2 * total, hipMemcpyDeviceToHost, st));
+                    TCHK(hipMemcpyAsync(out_origin_xy, oyd, sizeof(double) * 4 * total, hipMemcpyDeviceToHost, st));
+                }
+                if (out_err) TCHK(hipMemcpyAsync(out_err, oed, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, st));
+                TCHK(hipStreamSynchronize(st));
+            }
+            *out_n_points = total;
+            float ms = -1.f;
+            (void)hipEventElapsedTime(&ms, S->e0, S->e1);
+            g_last_ms = ms;
+        }
+    done:;
+        if (rc != SFMX_OK && S) (void)hipStreamSynchronize(st);   // nothing in flight from the pinned staging
+    }
+    if (rc == SFMX_EDEVICE) set_last_error("HIP error in sfmx_triangulate_matches");
+    if (rc == SFMX_ENOMEM) set_last_error("device allocation failed");
+    if (prev >= 0) (void)hipSetDevice(prev);
+    return rc;
+}
+
+}  // extern "C"

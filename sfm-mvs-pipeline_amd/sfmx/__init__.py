@@ -11,6 +11,7 @@ from .matching import (  # noqa: F401
     GridFeatureMatchingStrategy, calculate_shot_matches, match_pairs, pairs_unordered, pairs_video, pairs_grid,
 )
 
-from . import homography, scene, mvs, features  # noqa: F401,E402
+from . import homography, scene, mvs, features, triangulate  # noqa: F401,E402
+from .triangulate import triangulate_matches, triangulate_matches_device, triangulateMatch  # noqa: F401,E402
 
 __version__ = "0.1.0"

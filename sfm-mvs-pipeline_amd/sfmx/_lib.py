@@ -56,6 +56,11 @@ class sfmx_ba_options(C.Structure):
                 ("min_relative_decrease", C.c_double), ("max_group_points", C.c_int32), ("_reserved_opt", C.c_int32)]
 
 
+class sfmx_tri_camera(C.Structure):
+    """include/sfmx_triangulate.h"""
+    _fields_ = [("K", C.c_double * 9), ("dist", C.c_double * 5)]
+
+
 class sfmx_ba_plan_info(C.Structure):
     _fields_ = [("order", C.c_int32), ("leaf_tiles", C.c_int32), ("npad", C.c_int32), ("tiles", C.c_int32),
                 ("tiles_nz", C.c_int32), ("height", C.c_int32), ("leaves", C.c_int32), ("tasks", C.c_int32),
@@ -90,7 +95,7 @@ class sfmx_cli_config(C.Structure):
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
 
-# Every symbol include/sfmx.h (and include/sfmx_ba.h, sfmx_homography.h, sfmx_scene.h) declares, with its ctypes prototype.
+# Every symbol include/sfmx.h (and include/sfmx_ba.h, sfmx_homography.h, sfmx_triangulate.h, sfmx_scene.h) declares, with its ctypes prototype.
 _P = C.POINTER
 _i32p, _i64p, _vp = _P(C.c_int32), _P(C.c_int64), C.c_void_p
 PROTOTYPES = {
@@ -142,6 +147,10 @@ PROTOTYPES = {
     "sfmx_homography_ratios": (C.c_int, [_P(_vp), _i32p, C.c_int32, _i32p, _i32p, C.c_int32, _vp, _vp, C.c_double,
                                          C.c_int32, C.c_double, C.c_int32, C.c_int32, _vp, _P(C.c_double)]),
     "sfmx_homography_last_kernel_ms": (C.c_float, []),
+    "sfmx_triangulate_matches": (C.c_int, [_P(_vp), _i32p, C.c_int32, _P(sfmx_tri_camera), C.c_int32, _i32p,
+                                           _P(C.c_double), _i32p, C.c_int32, _vp, _vp, C.c_double, C.c_int32,
+                                           C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64p]),
+    "sfmx_triangulate_last_kernel_ms": (C.c_float, []),
     "sfmx_find_3d2d_matches": (C.c_int, [_P(_vp), _i32p, C.c_int32, _i32p, C.c_int32, _vp, _vp, _vp, C.c_int32,
                                          _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "sfmx_find_3d2d_last_kernel_ms": (C.c_float, []),
