@@ -66,6 +66,81 @@ int sfmx_ba_observations_from_origins(const int64_t* origin_offsets, int32_t n_p
                                       const double* origin_xy, int32_t n_shots, int32_t* obs_point, int32_t* obs_cam,
                                       double* obs_xy, int32_t* pose_of_shot, int32_t* shot_of_pose, int32_t* n_poses);
 
+#define SFMX_POINT_MERGE_DISTANCE   0.01   /* SfM.h:56 */
+#define SFMX_FEATURE_MERGE_DISTANCE 20.0   /* SfM.h:57 */
+
+/* The merge loop of SfM.cpp:354-363: Scene::mergePointcloudElement3d2d(element,
+ * pointMergeDistance, featureMergeDistance) (common/Scene.cpp:470-567) for the
+ * n_new elements in index order, the cloud growing as it goes.  Cloud and new
+ * elements are origin CSRs as above (sfmx_triangulate_matches' output is the
+ * case new_origin_offsets = 2 * arange).  For element e:
+ *   near    (:482-485)  cloud point c is a candidate iff !(d > point_merge_distance),
+ *                       d = cv::norm(c - e) = sqrt((dx*dx + dy*dy) + dz*dz) in double,
+ *                       so a NaN distance is a candidate; points appended earlier
+ *                       in the call are cloud points;
+ *   linked  (:498-545)  c qualifies iff for a record (s_e, q_e) of e and a record
+ *                       (s_c, q_c) c holds at that moment, s_e != s_c, the FIRST pair
+ *                       in list order joining {s_e, s_c} in either orientation has a
+ *                       DMatch with cv::Point2d(kp_left[queryIdx]) == the left shot's
+ *                       record, cv::Point2d(kp_right[trainIdx]) == the right shot's
+ *                       record and fabsf(distance) <= feature_merge_distance
+ *                       (match indices out of range never match);
+ *   best    (:532-538)  fold over the qualifying candidates in ascending index with
+ *                       `best == -1 || best > d` (the reference's single-thread order;
+ *                       its OpenMP order leaves ties open);
+ *   apply   (:552-567)  no winner: e is appended as given; winner c: each record of e,
+ *                       in order, is appended to c's list unless c already holds an
+ *                       equal (shot, xy) record (double ==; a NaN record is always
+ *                       appended) — PointcloudElement::addOrigin (:205-214) restated
+ *                       on origin points.
+ * Outputs: old points keep their indices and their records come first, merged-in
+ * records follow in merge order, appended elements follow in element order; the
+ * result is again an origin CSR for sfmx_find_3d2d_matches,
+ * sfmx_ba_observations_from_origins and the next merge.
+ *   out_target[e]          cloud index the element ended in
+ *   out_merge_distance[e]  distance to the point merged into (a NaN distance is the
+ *                          canonical quiet NaN), -1.0 if appended
+ *   out_xyz                capacity 3 * (n_cloud + n_new)
+ *   out_origin_offsets     capacity n_cloud + n_new + 1 (first *out_n_points + 1 valid)
+ *   out_origin_shot/_xy    capacity: cloud records + new records
+ *   out_n_points, out_n_origins   host memory, always
+ * The out_* arrays must not overlap the inputs (old records move within the CSR).
+ * SFMX_EINVAL (found on the host before any launch): a NaN merge distance, offsets
+ * that do not ascend from 0, an origin or pair shot outside [0, n_shots),
+ * n_cloud + n_new beyond int32.  n_new == 0 copies the cloud through and, with host
+ * inputs, touches no device.  A hash table that fills up: SFMX_EINTERNAL; more than
+ * 2^31 links among the new elements, 2^30 records in a cloud or 2^29 matches:
+ * SFMX_ECAPACITY (merge the elements in several calls).
+ * inputs_on_device = 1: keypoints[i], matches, pair_offsets, both clouds' arrays
+ * and the out_* arrays except the two counts are device pointers on `device`;
+ * 0: host memory.  In device mode the call stages through host memory: the
+ * per-element summaries and link lists of the sequential resolution, and both
+ * clouds' coordinates and origin records, which that resolution and the record
+ * dedupe read. */
+int sfmx_merge_pointcloud_3d2d(const sfmx_point2f* const* keypoints, const int32_t* n_keypoints, int32_t n_shots,
+                               const int32_t* pairs, int32_t n_pairs, const sfmx_dmatch* matches,
+                               const int64_t* pair_offsets, const double* cloud_xyz, int32_t n_cloud,
+                               const int64_t* cloud_origin_offsets, const int32_t* cloud_origin_shot,
+                               const double* cloud_origin_xy, const double* new_xyz, int32_t n_new,
+                               const int64_t* new_origin_offsets, const int32_t* new_origin_shot,
+                               const double* new_origin_xy, double point_merge_distance, double feature_merge_distance,
+                               int32_t inputs_on_device, int32_t device, void* stream, int32_t* out_target,
+                               double* out_merge_distance, double* out_xyz, int64_t* out_origin_offsets,
+                               int32_t* out_origin_shot, double* out_origin_xy, int32_t* out_n_points,
+                               int64_t* out_n_origins);
+
+/* Device time (ms) of the last sfmx_merge_pointcloud_3d2d call on this thread
+ * (table build + probe, link fill and scatter kernels, HIP events on its stream;
+ * the host resolution between them is not in it); 0 for n_new == 0, -1 before any call. */
+float sfmx_merge_pointcloud_last_kernel_ms(void);
+
+/* Counts of the last sfmx_merge_pointcloud_3d2d call on this thread (any pointer
+ * may be NULL): merges whose winner qualifies through a record it held when the
+ * call started (static), merges whose winner qualifies only through a record merged
+ * in earlier in the call or is a point appended in it (dynamic), and the links
+ * found among the new elements. */
+int sfmx_merge_pointcloud_last_stats(int64_t* merged_static, int64_t* merged_dynamic, int64_t* links);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,746 @@
+// SPDX-License-Identifier: MIT
+// sfmx point-cloud merge for gfx950.
+//
+//   sfmx_merge_pointcloud_3d2d   Scene::mergePointcloudElement3d2d (common/Scene.cpp:470-567), called
+//                                once per triangulated element by SfM.cpp:354-363
+//
+// The reference scans the whole cloud per new element for points within pointMergeDistance and then,
+// per (element origin point x candidate origin point), walks the shot-match list and that pair's DMatch
+// list comparing keypoint positions.  A candidate can only qualify through a DMatch that joins one of
+// the element's keypoints to one of the candidate's, so the qualifying candidates are reachable through
+// the match graph — a hash join, as in scene.hip:
+//   1. (host, O(pairs)) the first pair in list order per unordered shot pair — the only pair the
+//      reference's search loop can stop at (Scene.cpp:505-520);
+//   2. link table: every admissible DMatch of a first pair (valid indices, non-NaN positions,
+//      |distance| <= F) as two entries keyed by (shot, position bits), the partner entry is the other side;
+//   3. record tables: the cloud's records at call start and the new elements' records, keyed the same
+//      way, value = record index (its point / element index in a side array);
+//      all three tables are multi-valued: every entry claims a slot of its own (one 32-bit CAS, no key
+//      in the slot), a lookup walks the probe sequence to the first empty slot and compares the key of
+//      every entry it meets (cv::Point2d(kp.pt) == record, in double, as the reference);
+//   4. one thread per new element: records -> link entries -> partners -> cloud points holding the
+//      partner record, the fp64 near test, and the two values the fold rule needs (lowest-index
+//      qualifier with its distance; lowest-index minimum over non-NaN distances); the same walk against
+//      the new-record table counts, then fills, the earlier elements linked to this one;
+//   5. (host, sequential, O(n_new + links)) for e in order: static summary + the targets of its linked
+//      earlier elements, the fold (Scene.cpp:532-538), merge or append; then the record-level dedupe
+//      and every output record's destination.  A record added during the call always comes from an
+//      earlier new element, so "qualifies through a record added in this call" is exactly "linked to an
+//      earlier element and near that element's target";
+//   6. one scatter kernel writes the output xyz and origin CSR.
+// Integer / byte work with one fp64 distance per candidate: latency- and HBM-bound, no MFMA, no
+// floating-point atomics (one thread owns one element).  Built with -ffp-contract=off (host and device
+// evaluate the same uncontracted distance).
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/sfmx_scene.h"
+#include "match_common.hpp"
+
+namespace sfmx {
+namespace merge {
+
+// every NaN as the one quiet NaN 0x7ff8000000000000 (on the bits: a select on d != d may be folded away)
+__host__ __device__ __forceinline__ double canonical(double d) {
+    unsigned long long u;
+    memcpy(&u, &d, sizeof u);
+    if ((u & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) u = 0x7ff8000000000000ull;
+    memcpy(&d, &u, sizeof u);
+    return d;
+}
+
+// cv::norm(candidate - element) (Scene.cpp:482-485): sqrt(x*x + y*y + z*z) in double
+__host__ __device__ __forceinline__ double point_distance(const double* c, const double* e) {
+    const double dx = c[0] - e[0], dy = c[1] - e[1], dz = c[2] - e[2];
+    return canonical(sqrt((dx * dx + dy * dy) + dz * dz));
+}
+
+__device__ __forceinline__ unsigned long long pos_key(float x, float y) {
+    x = x == 0.f ? 0.f : x;   // -0 == +0 under cv::Point2d ==
+    y = y == 0.f ? 0.f : y;
+    return ((unsigned long long)__float_as_uint(x) << 32) | __float_as_uint(y);
+}
+__device__ __forceinline__ uint32_t mix(unsigned long long k, int shot) {
+    k ^= (unsigned long long)(uint32_t)(shot + 1) * 0x9e3779b97f4a7c15ull;
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
+    return (uint32_t)k;
+}
+
+// claim an empty slot for entry `id`; the loop is bounded by the capacity, a full table raises the flag
+__device__ __forceinline__ void insert(int32_t* __restrict__ slot, uint32_t cap, uint32_t h, int32_t id,
+                                       int32_t* __restrict__ full) {
+    h &= cap - 1;
+    for (uint32_t probe = 0; probe < cap; ++probe) {
+        if (atomicCAS(slot + h, -1, id) == -1) return;
+        h = (h + 1) & (cap - 1);
+    }
+    *full = 1;
+}
+
+// the record (x, y) as the float position it can equal, if any (NaN and non-representable doubles: none)
+__device__ __forceinline__ bool as_float_pos(double x, double y, float* fx, float* fy) {
+    *fx = (float)x;
+    *fy = (float)y;
+    return (double)*fx == x && (double)*fy == y;
+}
+
+// one thread per DMatch: the two link entries 2g (left side) and 2g + 1 (right side)
+__global__ __launch_bounds__(256)
+void build_links_kernel(int64_t n_matches, int n_pairs, const int64_t* __restrict__ off,
+                        const int32_t* __restrict__ pair_first, const int32_t* __restrict__ pairs,
+                        const DMatchDev* __restrict__ matches, const float2* const* __restrict__ kp,
+                        const int32_t* __restrict__ nkp, double F, int32_t* __restrict__ slot, uint32_t cap,
+                        int32_t* __restrict__ ent_shot, unsigned long long* __restrict__ ent_pos,
+                        int32_t* __restrict__ full) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_matches) return;
+    int lo = 0, hi = n_pairs - 1;   // the pair whose list holds match g
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= g) lo = mid; else hi = mid - 1;
+    }
+    if (!pair_first[lo]) return;   // a later duplicate of the unordered pair is never consulted
+    const DMatchDev d = matches[g];
+    const int L = pairs[2 * lo], R = pairs[2 * lo + 1];
+    if (d.queryIdx < 0 || d.queryIdx >= nkp[L] || d.trainIdx < 0 || d.trainIdx >= nkp[R]) return;
+    if (!((double)fabsf(d.distance) <= F)) return;   // NaN fails
+    const float2 a = kp[L][d.queryIdx], b = kp[R][d.trainIdx];
+    if (a.x != a.x || a.y != a.y || b.x != b.x || b.y != b.y) return;
+    const unsigned long long ka = pos_key(a.x, a.y), kb = pos_key(b.x, b.y);
+    ent_shot[2 * g] = L;
+    ent_pos[2 * g] = ka;
+    ent_shot[2 * g + 1] = R;
+    ent_pos[2 * g + 1] = kb;
+    insert(slot, cap, mix(ka, L), (int32_t)(2 * g), full);
+    insert(slot, cap, mix(kb, R), (int32_t)(2 * g + 1), full);
+}
+
+// one thread per origin record: its point and, if a keypoint position can equal it, its table entry
+__global__ __launch_bounds__(256)
+void build_records_kernel(int64_t n_rec, int n_pts, const int64_t* __restrict__ off,
+                          const int32_t* __restrict__ shot, const double* __restrict__ xy,
+                          int32_t* __restrict__ slot, uint32_t cap, int32_t* __restrict__ rec_point,
+                          int32_t* __restrict__ full) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rec) return;
+    int lo = 0, hi = n_pts - 1;   // the last point whose range starts at or before r (skips empty points)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= r) lo = mid; else hi = mid - 1;
+    }
+    rec_point[r] = lo;
+    float fx, fy;
+    if (!as_float_pos(xy[2 * r], xy[2 * r + 1], &fx, &fy)) return;
+    insert(slot, cap, mix(pos_key(fx, fy), shot[r]), (int32_t)r, full);
+}
+
+struct Table {             // a multi-valued record table
+    const int32_t* slot;
+    uint32_t cap;
+    const int32_t* shot;   // the records it indexes
+    const double* xy;
+    const int32_t* owner;  // record -> point / element
+};
+
+struct Summary {           // what the fold rule needs of an element's static candidates
+    int32_t first_idx;     // lowest-index qualifying cloud point, -1: none
+    int32_t min_idx;       // lowest-index point among the smallest non-NaN distances, -1: none
+    double first_d, min_d;
+};
+
+// one thread per new element.  FILL = false: the static summary and the number of earlier linked
+// elements; FILL = true: the list of those elements at link_off[e].
+template <bool FILL>
+__global__ __launch_bounds__(256)
+void probe_kernel(int n_new, const int64_t* __restrict__ new_off, const int32_t* __restrict__ new_shot,
+                  const double* __restrict__ new_xy, const double* __restrict__ new_xyz,
+                  const double* __restrict__ cloud_xyz, double D, const int32_t* __restrict__ lslot, uint32_t lcap,
+                  const int32_t* __restrict__ ent_shot, const unsigned long long* __restrict__ ent_pos, Table cloud,
+                  Table fresh, Summary* __restrict__ summary, int32_t* __restrict__ link_count,
+                  const int64_t* __restrict__ link_off, int32_t* __restrict__ link_list) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_new) return;
+    Summary s{-1, -1, 0.0, 0.0};
+    const double ex[3] = {new_xyz[3 * (int64_t)e], new_xyz[3 * (int64_t)e + 1], new_xyz[3 * (int64_t)e + 2]};
+    int32_t links = 0;
+    const int64_t out0 = FILL ? link_off[e] : 0;
+    const int32_t out_n = FILL ? (int32_t)(link_off[e + 1] - out0) : 0;
+    for (int64_t r = new_off[e]; r < new_off[e + 1]; ++r) {
+        float fx, fy;
+        if (!as_float_pos(new_xy[2 * r], new_xy[2 * r + 1], &fx, &fy)) continue;   // no keypoint can equal it
+        const int se = new_shot[r];
+        const unsigned long long key = pos_key(fx, fy);
+        uint32_t h = mix(key, se) & (lcap - 1);
+        for (uint32_t probe = 0; probe < lcap; ++probe, h = (h + 1) & (lcap - 1)) {
+            const int32_t i = lslot[h];
+            if (i < 0) break;
+            if (ent_shot[i] != se || ent_pos[i] != key) continue;
+            // a DMatch of the first pair joining {se, sc} with this record on se's side: its other side
+            const int sc = ent_shot[i ^ 1];
+            const unsigned long long pk = ent_pos[i ^ 1];
+            const double px = (double)__uint_as_float((uint32_t)(pk >> 32)), py = (double)__uint_as_float((uint32_t)pk);
+            const uint32_t ph = mix(pk, sc);
+            if (!FILL) {
+                uint32_t g = ph & (cloud.cap - 1);
+                for (uint32_t q = 0; q < cloud.cap; ++q, g = (g + 1) & (cloud.cap - 1)) {
+                    const int32_t j = cloud.slot[g];
+                    if (j < 0) break;
+                    if (cloud.shot[j] != sc || cloud.xy[2 * (int64_t)j] != px || cloud.xy[2 * (int64_t)j + 1] != py) continue;
+                    const int32_t c = cloud.owner[j];
+                    const double d = point_distance(cloud_xyz + 3 * (int64_t)c, ex);
+                    if (d > D) continue;   // Scene.cpp:483: a NaN distance stays a candidate
+                    if (s.first_idx < 0 || c < s.first_idx) { s.first_idx = c; s.first_d = d; }
+                    if (d == d && (s.min_idx < 0 || d < s.min_d || (d == s.min_d && c < s.min_idx))) { s.min_idx = c; s.min_d = d; }
+                }
+            }
+            uint32_t g = ph & (fresh.cap - 1);
+            for (uint32_t q = 0; q < fresh.cap; ++q, g = (g + 1) & (fresh.cap - 1)) {
+                const int32_t j = fresh.slot[g];
+                if (j < 0) break;
+                if (fresh.shot[j] != sc || fresh.xy[2 * (int64_t)j] != px || fresh.xy[2 * (int64_t)j + 1] != py) continue;
+                const int32_t e2 = fresh.owner[j];
+                if (e2 >= e) continue;
+                if (FILL) { if (links < out_n) link_list[out0 + links] = e2; }
+                if (links < INT32_MAX) ++links;   // saturates: the host refuses a total beyond int32
+            }
+        }
+    }
+    if (!FILL) {
+        summary[e] = s;
+        link_count[e] = links;
+    }
+}
+
+// one thread per cloud record, new record and output point
+__global__ __launch_bounds__(256)
+void scatter_kernel(int64_t n_crec, int64_t n_nrec, int n_cloud, int n_out, const int64_t* __restrict__ cloud_off,
+                    const int32_t* __restrict__ crec_point, const int32_t* __restrict__ cloud_shot,
+                    const double* __restrict__ cloud_xy, const double* __restrict__ cloud_xyz,
+                    const int32_t* __restrict__ new_shot, const double* __restrict__ new_xy,
+                    const double* __restrict__ new_xyz, const int64_t* __restrict__ new_dest,
+                    const int32_t* __restrict__ appended, const int64_t* __restrict__ out_off,
+                    int32_t* __restrict__ out_shot, double* __restrict__ out_xy, double* __restrict__ out_xyz) {
+    int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < n_crec) {   // old records keep their place at the head of their point's list
+        const int p = crec_point[g];
+        const int64_t dst = out_off[p] + (g - cloud_off[p]);
+        out_shot[dst] = cloud_shot[g];
+        out_xy[2 * dst] = cloud_xy[2 * g];
+        out_xy[2 * dst + 1] = cloud_xy[2 * g + 1];
+        return;
+    }
+    g -= n_crec;
+    if (g < n_nrec) {
+        const int64_t dst = new_dest[g];
+        if (dst < 0) return;   // a record its target already held
+        out_shot[dst] = new_shot[g];
+        out_xy[2 * dst] = new_xy[2 * g];
+        out_xy[2 * dst + 1] = new_xy[2 * g + 1];
+        return;
+    }
+    g -= n_nrec;
+    if (g < n_out) {
+        const double* src = g < n_cloud ? cloud_xyz + 3 * g : new_xyz + 3 * (int64_t)appended[g - n_cloud];
+        out_xyz[3 * g] = src[0];
+        out_xyz[3 * g + 1] = src[1];
+        out_xyz[3 * g + 2] = src[2];
+    }
+}
+
+thread_local float g_last_ms = -1.f;
+thread_local int64_t g_last_stats[3] = {0, 0, 0};   // merges decided statically, dynamically; new-new links
+
+struct Bufs {               // device work buffers: the requests of a call are served by one allocation
+    struct Request { void** where; size_t bytes; };
+    std::vector<void*> ptrs;
+    std::vector<Request> requests;
+    ~Bufs() { for (void* q : ptrs) (void)hipFree(q); }
+    void* alloc(size_t bytes) {
+        void* q = nullptr;
+        if (hipMalloc(&q, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
+        ptrs.push_back(q);
+        return q;
+    }
+    template <class T> void want(T*& p, int64_t n) {   // p is set by commit()
+        p = nullptr;
+        requests.push_back({reinterpret_cast<void**>(&p), (sizeof(T) * (size_t)std::max<int64_t>(n, 1) + 255) & ~(size_t)255});
+    }
+    bool commit() {
+        size_t total = 0;
+        for (const Request& r : requests) total += r.bytes;
+        char* q = static_cast<char*>(alloc(total));
+        if (!q) return false;
+        for (const Request& r : requests) { *r.where = q; q += r.bytes; }
+        requests.clear();
+        return true;
+    }
+};
+
+struct SyncOnExit {        // declared after the host buffers of the async copies: the stream drains before they go
+    hipStream_t st;
+    const bool* armed;     // the device was selected (a host-only call touches no device)
+    ~SyncOnExit() { if (*armed) (void)hipStreamSynchronize(st); }
+};
+
+struct Events {            // the three timed spans of a call
+    hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+static uint32_t capacity_for(int64_t entries) {   // power of two, load factor <= 1/2
+    uint32_t cap = 16;
+    while ((int64_t)cap < 2 * entries) cap <<= 1;
+    return cap;
+}
+
+static bool offsets_ok(const int64_t* off, int32_t n) {
+    if (off[0] != 0) return false;
+    for (int32_t i = 0; i < n; ++i)
+        if (off[i + 1] < off[i]) return false;
+    return true;
+}
+
+}  // namespace merge
+}  // namespace sfmx
+
+using namespace sfmx;
+using namespace sfmx::merge;
+
+#define MCHK(expr) do { if ((expr) != hipSuccess) { rc = SFMX_EDEVICE; set_last_error("HIP error in " #expr); goto done; } } while (0)
+#define MFAIL(code, msg) do { rc = (code); set_last_error(msg); goto done; } while (0)
+
+extern "C" {
+
+float sfmx_merge_pointcloud_last_kernel_ms(void) { return g_last_ms; }
+
+int sfmx_merge_pointcloud_last_stats(int64_t* merged_static, int64_t* merged_dynamic, int64_t* links) {
+    if (merged_static) *merged_static = g_last_stats[0];
+    if (merged_dynamic) *merged_dynamic = g_last_stats[1];
+    if (links) *links = g_last_stats[2];
+    return SFMX_OK;
+}
+
+int sfmx_merge_pointcloud_3d2d(const sfmx_point2f* const* keypoints, const int32_t* n_keypoints, int32_t n_shots,
+                               const int32_t* pairs, int32_t n_pairs, const sfmx_dmatch* matches,
+                               const int64_t* pair_offsets, const double* cloud_xyz, int32_t n_cloud,
+                               const int64_t* cloud_origin_offsets, const int32_t* cloud_origin_shot,
+                               const double* cloud_origin_xy, const double* new_xyz, int32_t n_new,
+                               const int64_t* new_origin_offsets, const int32_t* new_origin_shot,
+                               const double* new_origin_xy, double point_merge_distance, double feature_merge_distance,
+                               int32_t inputs_on_device, int32_t device, void* stream, int32_t* out_target,
+                               double* out_merge_distance, double* out_xyz, int64_t* out_origin_offsets,
+                               int32_t* out_origin_shot, double* out_origin_xy, int32_t* out_n_points,
+                               int64_t* out_n_origins) {
+    if (n_shots < 0 || n_pairs < 0 || n_cloud < 0 || n_new < 0) { set_last_error("negative count"); return SFMX_EINVAL; }
+    if ((int64_t)n_cloud + n_new > INT32_MAX) { set_last_error("cloud and new points together exceed the int32 range"); return SFMX_EINVAL; }
+    if (point_merge_distance != point_merge_distance || feature_merge_distance != feature_merge_distance) {
+        set_last_error("a merge distance is NaN");
+        return SFMX_EINVAL;
+    }
+    if ((n_shots && (!keypoints || !n_keypoints)) || (n_pairs && (!pairs || !pair_offsets)) || !cloud_origin_offsets ||
+        !new_origin_offsets || (n_cloud && !cloud_xyz) || (n_new && (!new_xyz || !out_target || !out_merge_distance)) ||
+        !out_origin_offsets || !out_n_points || !out_n_origins || (n_cloud + n_new && !out_xyz)) {
+        set_last_error("null argument");
+        return SFMX_EINVAL;
+    }
+    for (int p = 0; p < n_pairs; ++p)
+        if (pairs[2 * p] < 0 || pairs[2 * p] >= n_shots || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= n_shots) {
+            set_last_error("pair shot index out of range");
+            return SFMX_EINVAL;
+        }
+    const hipStream_t st = (hipStream_t)stream;
+    const double D = point_merge_distance, F = feature_merge_distance;
+    int prev = -1;
+    bool device_set = false;
+    int rc = SFMX_OK;
+    try {
+        Bufs b;
+        // host copies of what the host resolution reads (staged from the device when inputs_on_device)
+        std::vector<int64_t> hoff(n_pairs + 1, 0), hco(n_cloud + 1, 0), hno(n_new + 1, 0);
+        std::vector<int32_t> hcs, hns;
+        std::vector<double> hcxy, hnxy, hcx, hnx;
+        const int64_t *co = cloud_origin_offsets, *no = new_origin_offsets;
+        const int32_t *cs = cloud_origin_shot, *ns = new_origin_shot;
+        const double *cxy = cloud_origin_xy, *nxy = new_origin_xy, *cx = cloud_xyz, *nx = new_xyz;
+        int64_t n_crec = 0, n_nrec = 0, n_matches = 0;
+        const SyncOnExit drain_staging{st, &device_set};
+        if (inputs_on_device) {
+            int ndev = 0;
+            if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) MFAIL(SFMX_EDEVICE, "no HIP device visible");
+            if (device < 0 || device >= ndev) MFAIL(SFMX_EINVAL, "device index out of range");
+            (void)hipGetDevice(&prev);
+            if (hipSetDevice(device) != hipSuccess) MFAIL(SFMX_EDEVICE, "cannot select the device");
+            device_set = true;
+            if (n_pairs) MCHK(hipMemcpyAsync(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
+            MCHK(hipMemcpyAsync(hco.data(), cloud_origin_offsets, sizeof(int64_t) * (n_cloud + 1), hipMemcpyDeviceToHost, st));
+            MCHK(hipMemcpyAsync(hno.data(), new_origin_offsets, sizeof(int64_t) * (n_new + 1), hipMemcpyDeviceToHost, st));
+            MCHK(hipStreamSynchronize(st));
+            co = hco.data();
+            no = hno.data();
+        } else if (n_pairs) {
+            std::memcpy(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1));
+        }
+        if (!offsets_ok(hoff.data(), n_pairs)) MFAIL(SFMX_EINVAL, "pair offsets do not ascend from 0");
+        if (!offsets_ok(co, n_cloud)) MFAIL(SFMX_EINVAL, "cloud origin offsets do not ascend from 0");
+        if (!offsets_ok(no, n_new)) MFAIL(SFMX_EINVAL, "new origin offsets do not ascend from 0");
+        n_crec = co[n_cloud];
+        n_nrec = no[n_new];
+        n_matches = hoff[n_pairs];
+        // table capacities (2 x entries, rounded up to a power of two) and entry indices stay within 32 bits
+        if (n_crec > (1 << 30) || n_nrec > (1 << 30) || n_matches > (1 << 29)) MFAIL(SFMX_ECAPACITY, "too many origin records or matches for one call");
+        if ((n_crec && (!cloud_origin_shot || !cloud_origin_xy)) || (n_nrec && (!new_origin_shot || !new_origin_xy)) ||
+            (n_crec + n_nrec && (!out_origin_shot || !out_origin_xy)) || (n_matches && !matches))
+            MFAIL(SFMX_EINVAL, "null argument");
+        if (inputs_on_device) {
+            hcs.resize(n_crec); hcxy.resize(2 * n_crec); hcx.resize(3 * (size_t)n_cloud);
+            hns.resize(n_nrec); hnxy.resize(2 * n_nrec); hnx.resize(3 * (size_t)n_new);
+            if (n_crec) {
+                MCHK(hipMemcpyAsync(hcs.data(), cloud_origin_shot, sizeof(int32_t) * n_crec, hipMemcpyDeviceToHost, st));
+                MCHK(hipMemcpyAsync(hcxy.data(), cloud_origin_xy, sizeof(double) * 2 * n_crec, hipMemcpyDeviceToHost, st));
+            }
+            if (n_nrec) {
+                MCHK(hipMemcpyAsync(hns.data(), new_origin_shot, sizeof(int32_t) * n_nrec, hipMemcpyDeviceToHost, st));
+                MCHK(hipMemcpyAsync(hnxy.data(), new_origin_xy, sizeof(double) * 2 * n_nrec, hipMemcpyDeviceToHost, st));
+            }
+            if (n_cloud) MCHK(hipMemcpyAsync(hcx.data(), cloud_xyz, sizeof(double) * 3 * n_cloud, hipMemcpyDeviceToHost, st));
+            if (n_new) MCHK(hipMemcpyAsync(hnx.data(), new_xyz, sizeof(double) * 3 * n_new, hipMemcpyDeviceToHost, st));
+            MCHK(hipStreamSynchronize(st));
+            cs = hcs.data(); cxy = hcxy.data(); cx = hcx.data();
+            ns = hns.data(); nxy = hnxy.data(); nx = hnx.data();
+        }
+        for (int64_t r = 0; r < n_crec; ++r)
+            if (cs[r] < 0 || cs[r] >= n_shots) MFAIL(SFMX_EINVAL, "cloud origin shot out of range");
+        for (int64_t r = 0; r < n_nrec; ++r)
+            if (ns[r] < 0 || ns[r] >= n_shots) MFAIL(SFMX_EINVAL, "new origin shot out of range");
+
+        if (n_new == 0) {   // nothing to merge: the cloud goes through unchanged, no kernel
+            if (inputs_on_device) {
+                if (n_cloud) MCHK(hipMemcpyAsync(out_xyz, cloud_xyz, sizeof(double) * 3 * n_cloud, hipMemcpyDeviceToDevice, st));
+                MCHK(hipMemcpyAsync(out_origin_offsets, cloud_origin_offsets, sizeof(int64_t) * (n_cloud + 1), hipMemcpyDeviceToDevice, st));
+                if (n_crec) {
+                    MCHK(hipMemcpyAsync(out_origin_shot, cloud_origin_shot, sizeof(int32_t) * n_crec, hipMemcpyDeviceToDevice, st));
+                    MCHK(hipMemcpyAsync(out_origin_xy, cloud_origin_xy, sizeof(double) * 2 * n_crec, hipMemcpyDeviceToDevice, st));
+                }
+                MCHK(hipStreamSynchronize(st));
+            } else {
+                if (n_cloud) std::memcpy(out_xyz, cloud_xyz, sizeof(double) * 3 * n_cloud);
+                std::memcpy(out_origin_offsets, cloud_origin_offsets, sizeof(int64_t) * (n_cloud + 1));
+                if (n_crec) {
+                    std::memcpy(out_origin_shot, cloud_origin_shot, sizeof(int32_t) * n_crec);
+                    std::memcpy(out_origin_xy, cloud_origin_xy, sizeof(double) * 2 * n_crec);
+                }
+            }
+            *out_n_points = n_cloud;
+            *out_n_origins = n_crec;
+            g_last_ms = 0.f;
+            g_last_stats[0] = g_last_stats[1] = g_last_stats[2] = 0;
+            goto done;
+        }
+
+        if (!device_set) {
+            int ndev = 0;
+            if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) MFAIL(SFMX_EDEVICE, "no HIP device visible");
+            if (device < 0 || device >= ndev) MFAIL(SFMX_EINVAL, "device index out of range");
+            (void)hipGetDevice(&prev);
+            if (hipSetDevice(device) != hipSuccess) MFAIL(SFMX_EDEVICE, "cannot select the device");
+            device_set = true;
+        }
+        {
+            hipDeviceProp_t prop;
+            if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+                MFAIL(SFMX_EDEVICE, "sfmx kernels are built for gfx950 only");
+        }
+        {
+            // 1. first pair per unordered shot pair (Scene.cpp:505-520: the loop breaks at the first pair
+            //    joining the two shots in either orientation); a pair of a shot with itself joins nothing
+            std::vector<int32_t> pair_first(std::max(n_pairs, 1), 0);
+            int64_t link_matches = 0;
+            {
+                std::vector<std::pair<int64_t, int32_t>> keyed(n_pairs);
+                for (int p = 0; p < n_pairs; ++p) {
+                    const int64_t a = std::min(pairs[2 * p], pairs[2 * p + 1]), c = std::max(pairs[2 * p], pairs[2 * p + 1]);
+                    keyed[p] = {a * n_shots + c, p};
+                }
+                std::sort(keyed.begin(), keyed.end());
+                for (int i = 0; i < n_pairs; ++i) {
+                    const int p = keyed[i].second;
+                    if (pairs[2 * p] == pairs[2 * p + 1]) continue;
+                    if (i == 0 || keyed[i - 1].first != keyed[i].first) {
+                        pair_first[p] = 1;
+                        link_matches += hoff[p + 1] - hoff[p];
+                    }
+                }
+            }
+            const uint32_t lcap = capacity_for(2 * link_matches), ccap = capacity_for(n_crec), ncap = capacity_for(n_nrec);
+            const int n_total = n_cloud + n_new;
+
+            // device views of the inputs and outputs
+            std::vector<const float2*> kptr(std::max(n_shots, 1), nullptr);
+            const DMatchDev* dm = reinterpret_cast<const DMatchDev*>(matches);
+            const int64_t *doff = pair_offsets, *dco = cloud_origin_offsets, *dno = new_origin_offsets;
+            const int32_t *dcs = cloud_origin_shot, *dns = new_origin_shot;
+            const double *dcxy = cloud_origin_xy, *dnxy = new_origin_xy, *dcx = cloud_xyz, *dnx = new_xyz;
+            int32_t* do_shot = out_origin_shot;
+            double *do_xy = out_origin_xy, *do_xyz = out_xyz;
+            int64_t* do_off = out_origin_offsets;
+            // work buffers: requested below, all served by one allocation (Bufs::commit)
+            float2* kd = nullptr;
+            DMatchDev* md = nullptr;
+            int64_t *od = nullptr, *cod = nullptr, *nod = nullptr, *loff = nullptr, *ndest = nullptr;
+            int32_t *csd = nullptr, *nsd = nullptr, *nkd = nullptr, *prd = nullptr, *pfd = nullptr, *lslot = nullptr, *cslot = nullptr,
+                    *nslot = nullptr, *ent_shot = nullptr, *crec_point = nullptr, *nrec_elem = nullptr, *full = nullptr,
+                    *lcount = nullptr, *appd = nullptr;
+            double *cxyd = nullptr, *nxyd = nullptr, *cxd = nullptr, *nxd = nullptr;
+            const float2** kpd = nullptr;
+            unsigned long long* ent_pos = nullptr;
+            Summary* summ = nullptr;
+            if (inputs_on_device) {
+                for (int i = 0; i < n_shots; ++i) kptr[i] = reinterpret_cast<const float2*>(keypoints[i]);
+            } else {
+                int64_t nk = 0;
+                for (int i = 0; i < n_shots; ++i) {
+                    if (n_keypoints[i] < 0) MFAIL(SFMX_EINVAL, "negative keypoint count");
+                    nk += n_keypoints[i];
+                }
+                b.want(kd, nk);
+                b.want(md, n_matches);
+                b.want(od, n_pairs + 1);
+                b.want(cod, n_cloud + 1);
+                b.want(nod, n_new + 1);
+                b.want(csd, n_crec);
+                b.want(nsd, n_nrec);
+                b.want(cxyd, 2 * n_crec);
+                b.want(nxyd, 2 * n_nrec);
+                b.want(cxd, 3 * (int64_t)n_cloud);
+                b.want(nxd, 3 * (int64_t)n_new);
+                b.want(do_shot, n_crec + n_nrec);
+                b.want(do_xy, 2 * (n_crec + n_nrec));
+                b.want(do_xyz, 3 * (int64_t)n_total);
+                b.want(do_off, (int64_t)n_total + 1);
+            }
+            b.want(kpd, (int64_t)kptr.size());
+            b.want(nkd, n_shots);
+            b.want(prd, 2 * (int64_t)n_pairs);
+            b.want(pfd, n_pairs);
+            b.want(lslot, lcap);
+            b.want(cslot, ccap);
+            b.want(nslot, ncap);
+            b.want(ent_shot, 2 * n_matches);
+            b.want(ent_pos, 2 * n_matches);
+            b.want(crec_point, n_crec);
+            b.want(nrec_elem, n_nrec);
+            b.want(full, 1);
+            b.want(summ, n_new);
+            b.want(lcount, n_new);
+            b.want(loff, (int64_t)n_new + 1);
+            b.want(ndest, n_nrec);
+            b.want(appd, n_new);
+            if (!b.commit()) MFAIL(SFMX_ENOMEM, "device allocation failed");
+            if (!inputs_on_device) {
+                int64_t o = 0;
+                for (int i = 0; i < n_shots; ++i) {
+                    if (n_keypoints[i]) MCHK(hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st));
+                    kptr[i] = kd + o;
+                    o += n_keypoints[i];
+                }
+                if (n_matches) MCHK(hipMemcpyAsync(md, matches, sizeof(DMatchDev) * n_matches, hipMemcpyHostToDevice, st));
+                MCHK(hipMemcpyAsync(od, hoff.data(), sizeof(int64_t) * (n_pairs + 1), hipMemcpyHostToDevice, st));
+                MCHK(hipMemcpyAsync(cod, co, sizeof(int64_t) * (n_cloud + 1), hipMemcpyHostToDevice, st));
+                MCHK(hipMemcpyAsync(nod, no, sizeof(int64_t) * (n_new + 1), hipMemcpyHostToDevice, st));
+                if (n_crec) {
+                    MCHK(hipMemcpyAsync(csd, cs, sizeof(int32_t) * n_crec, hipMemcpyHostToDevice, st));
+                    MCHK(hipMemcpyAsync(cxyd, cxy, sizeof(double) * 2 * n_crec, hipMemcpyHostToDevice, st));
+                }
+                if (n_nrec) {
+                    MCHK(hipMemcpyAsync(nsd, ns, sizeof(int32_t) * n_nrec, hipMemcpyHostToDevice, st));
+                    MCHK(hipMemcpyAsync(nxyd, nxy, sizeof(double) * 2 * n_nrec, hipMemcpyHostToDevice, st));
+                }
+                if (n_cloud) MCHK(hipMemcpyAsync(cxd, cx, sizeof(double) * 3 * n_cloud, hipMemcpyHostToDevice, st));
+                MCHK(hipMemcpyAsync(nxd, nx, sizeof(double) * 3 * n_new, hipMemcpyHostToDevice, st));
+                dm = md; doff = od; dco = cod; dno = nod; dcs = csd; dns = nsd; dcxy = cxyd; dnxy = nxyd; dcx = cxd; dnx = nxd;
+            }
+            MCHK(hipMemcpyAsync(kpd, kptr.data(), sizeof(float2*) * kptr.size(), hipMemcpyHostToDevice, st));
+            if (n_shots) MCHK(hipMemcpyAsync(nkd, n_keypoints, sizeof(int32_t) * n_shots, hipMemcpyHostToDevice, st));
+            if (n_pairs) {
+                MCHK(hipMemcpyAsync(prd, pairs, sizeof(int32_t) * 2 * n_pairs, hipMemcpyHostToDevice, st));
+                MCHK(hipMemcpyAsync(pfd, pair_first.data(), sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, st));
+            }
+            Events events;
+            hipEvent_t* ev = events.e;
+            for (int i = 0; i < 6; ++i) MCHK(hipEventCreate(&ev[i]));
+            const Table tc{cslot, ccap, dcs, dcxy, crec_point}, tn{nslot, ncap, dns, dnxy, nrec_elem};
+            const unsigned eb = (unsigned)((n_new + 255) / 256);
+            std::vector<Summary> hs(n_new);
+            std::vector<int32_t> hcount(n_new), hlist, htarget(n_new), happ;
+            std::vector<int64_t> hloff(n_new + 1, 0), hdest(n_nrec, -1), hout((size_t)n_total + 1, 0);
+            std::vector<double> hdist(n_new);
+            const SyncOnExit drain{st, &device_set};
+            int32_t hfull = 0;
+            int n_app = 0;
+
+            // 2-4. tables, static probe, link count
+            MCHK(hipEventRecord(ev[0], st));
+            MCHK(hipMemsetAsync(lslot, 0xff, sizeof(int32_t) * lcap, st));
+            MCHK(hipMemsetAsync(cslot, 0xff, sizeof(int32_t) * ccap, st));
+            MCHK(hipMemsetAsync(nslot, 0xff, sizeof(int32_t) * ncap, st));
+            MCHK(hipMemsetAsync(full, 0, sizeof(int32_t), st));
+            if (n_matches && link_matches)
+                build_links_kernel<<<(unsigned)((n_matches + 255) / 256), 256, 0, st>>>(n_matches, n_pairs, doff, pfd, prd, dm, kpd, nkd,
+                                                                                       F, lslot, lcap, ent_shot, ent_pos, full);
+            if (n_crec)
+                build_records_kernel<<<(unsigned)((n_crec + 255) / 256), 256, 0, st>>>(n_crec, n_cloud, dco, dcs, dcxy, cslot, ccap,
+                                                                                     crec_point, full);
+            if (n_nrec)
+                build_records_kernel<<<(unsigned)((n_nrec + 255) / 256), 256, 0, st>>>(n_nrec, n_new, dno, dns, dnxy, nslot, ncap,
+                                                                                     nrec_elem, full);
+            probe_kernel<false><<<eb, 256, 0, st>>>(n_new, dno, dns, dnxy, dnx, dcx, D, lslot, lcap, ent_shot, ent_pos, tc, tn, summ,
+                                                    lcount, nullptr, nullptr);
+            MCHK(hipGetLastError());
+            MCHK(hipEventRecord(ev[1], st));
+            MCHK(hipMemcpyAsync(hs.data(), summ, sizeof(Summary) * n_new, hipMemcpyDeviceToHost, st));
+            MCHK(hipMemcpyAsync(hcount.data(), lcount, sizeof(int32_t) * n_new, hipMemcpyDeviceToHost, st));
+            MCHK(hipMemcpyAsync(&hfull, full, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            MCHK(hipStreamSynchronize(st));
+            if (hfull) MFAIL(SFMX_EINTERNAL, "a merge hash table filled up");
+            for (int e = 0; e < n_new; ++e) hloff[e + 1] = hloff[e] + hcount[e];
+            if (hloff[n_new] >= INT32_MAX) MFAIL(SFMX_ECAPACITY, "more than 2^31 links between the new elements: merge them in several calls");
+            hlist.resize(hloff[n_new]);
+            MCHK(hipEventRecord(ev[2], st));
+            if (hloff[n_new]) {
+                auto* llist = static_cast<int32_t*>(b.alloc(sizeof(int32_t) * (size_t)hloff[n_new]));
+                if (!llist) MFAIL(SFMX_ENOMEM, "device allocation failed");
+                MCHK(hipMemcpyAsync(loff, hloff.data(), sizeof(int64_t) * (n_new + 1), hipMemcpyHostToDevice, st));
+                probe_kernel<true><<<eb, 256, 0, st>>>(n_new, dno, dns, dnxy, dnx, dcx, D, lslot, lcap, ent_shot, ent_pos, tc, tn,
+                                                       nullptr, nullptr, loff, llist);
+                MCHK(hipGetLastError());
+                MCHK(hipEventRecord(ev[3], st));
+                MCHK(hipMemcpyAsync(hlist.data(), llist, sizeof(int32_t) * hloff[n_new], hipMemcpyDeviceToHost, st));
+                MCHK(hipStreamSynchronize(st));
+            } else {
+                MCHK(hipEventRecord(ev[3], st));
+            }
+
+            // 5a. targets, in element order (Scene.cpp:532-538 fold, :552-567 merge or append)
+            happ.reserve(n_new);
+            int64_t n_static = 0, n_dynamic = 0;
+            for (int e = 0; e < n_new; ++e) {
+                Summary s = hs[e];
+                bool first_dynamic = false, min_dynamic = false;   // the slot holds a candidate only this call made
+                for (int64_t k = hloff[e]; k < hloff[e + 1]; ++k) {
+                    const int32_t c = htarget[hlist[k]];
+                    const double* pc = c < n_cloud ? cx + 3 * (int64_t)c : nx + 3 * (int64_t)happ[c - n_cloud];
+                    const double d = point_distance(pc, nx + 3 * (int64_t)e);
+                    if (d > D) continue;
+                    // a point that also qualifies statically never displaces the static slots: it is behind or in them
+                    if (s.first_idx < 0 || c < s.first_idx) { s.first_idx = c; s.first_d = d; first_dynamic = true; }
+                    if (d == d && (s.min_idx < 0 || d < s.min_d || (d == s.min_d && c < s.min_idx))) { s.min_idx = c; s.min_d = d; min_dynamic = true; }
+                }
+                if (s.first_idx < 0) {
+                    htarget[e] = n_cloud + n_app++;
+                    hdist[e] = -1.0;
+                    happ.push_back(e);
+                } else if (s.first_d != s.first_d) {   // best stays NaN: `best > d` is never true again
+                    htarget[e] = s.first_idx;
+                    hdist[e] = s.first_d;
+                    ++(first_dynamic ? n_dynamic : n_static);
+                } else {
+                    htarget[e] = s.min_idx;
+                    hdist[e] = s.min_d;
+                    ++(min_dynamic ? n_dynamic : n_static);
+                }
+            }
+            g_last_stats[0] = n_static;
+            g_last_stats[1] = n_dynamic;
+            g_last_stats[2] = hloff[n_new];
+            // 5b. record-level dedupe and destinations: old records, then merged-in records in merge order.
+            //     The merged elements are grouped by target (stable, so in merge order); one pass over the
+            //     output points in index order then knows every list's start as it goes.
+            const int n_out = n_cloud + n_app;
+            {
+                std::vector<int64_t> gstart((size_t)n_out + 2, 0);
+                for (int e = 0; e < n_new; ++e)
+                    if (hdist[e] != -1.0) ++gstart[htarget[e] + 2];
+                for (int c = 0; c < n_out; ++c) gstart[c + 2] += gstart[c + 1];
+                std::vector<int32_t> gelem(gstart[n_out + 1]);
+                for (int e = 0; e < n_new; ++e)
+                    if (hdist[e] != -1.0) gelem[gstart[htarget[e] + 1]++] = e;   // gstart[c + 1] ends as the end of c's group
+                std::vector<int64_t> cur;   // new-record indices merged into the current point
+                for (int c = 0; c < n_out; ++c) {
+                    const int e0 = c < n_cloud ? -1 : happ[c - n_cloud];
+                    const int64_t i0 = e0 < 0 ? co[c] : no[e0], ni = (e0 < 0 ? co[c + 1] : no[e0 + 1]) - i0;
+                    const int32_t* is = (e0 < 0 ? cs : ns) + i0;
+                    const double* ixy = (e0 < 0 ? cxy : nxy) + 2 * i0;
+                    if (e0 >= 0)
+                        for (int64_t k = 0; k < ni; ++k) hdest[i0 + k] = hout[c] + k;   // appended as given
+                    cur.clear();
+                    for (int64_t g = gstart[c]; g < gstart[c + 1]; ++g) {
+                        const int e = gelem[g];
+                        for (int64_t r = no[e]; r < no[e + 1]; ++r) {
+                            bool held = false;
+                            for (int64_t k = 0; k < ni && !held; ++k)
+                                held = is[k] == ns[r] && ixy[2 * k] == nxy[2 * r] && ixy[2 * k + 1] == nxy[2 * r + 1];
+                            for (size_t k = 0; k < cur.size() && !held; ++k) {
+                                const int64_t q = cur[k];
+                                held = ns[q] == ns[r] && nxy[2 * q] == nxy[2 * r] && nxy[2 * q + 1] == nxy[2 * r + 1];
+                            }
+                            if (!held) {
+                                hdest[r] = hout[c] + ni + (int64_t)cur.size();
+                                cur.push_back(r);
+                            }
+                        }
+                    }
+                    hout[c + 1] = hout[c] + ni + (int64_t)cur.size();
+                }
+            }
+
+            // 6. scatter
+            if (n_nrec) MCHK(hipMemcpyAsync(ndest, hdest.data(), sizeof(int64_t) * n_nrec, hipMemcpyHostToDevice, st));
+            if (n_app) MCHK(hipMemcpyAsync(appd, happ.data(), sizeof(int32_t) * n_app, hipMemcpyHostToDevice, st));
+            MCHK(hipMemcpyAsync(do_off, hout.data(), sizeof(int64_t) * (n_out + 1), hipMemcpyHostToDevice, st));
+            MCHK(hipEventRecord(ev[4], st));
+            {
+                const int64_t items = n_crec + n_nrec + n_out;
+                scatter_kernel<<<(unsigned)((items + 255) / 256), 256, 0, st>>>(n_crec, n_nrec, n_cloud, n_out, dco, crec_point, dcs, dcxy,
+                                                                               dcx, dns, dnxy, dnx, ndest, appd, do_off, do_shot, do_xy,
+                                                                               do_xyz);
+            }
+            MCHK(hipGetLastError());
+            MCHK(hipEventRecord(ev[5], st));
+            if (inputs_on_device) {
+                MCHK(hipMemcpyAsync(out_target, htarget.data(), sizeof(int32_t) * n_new, hipMemcpyHostToDevice, st));
+                MCHK(hipMemcpyAsync(out_merge_distance, hdist.data(), sizeof(double) * n_new, hipMemcpyHostToDevice, st));
+            } else {
+                std::memcpy(out_target, htarget.data(), sizeof(int32_t) * n_new);
+                std::memcpy(out_merge_distance, hdist.data(), sizeof(double) * n_new);
+                std::memcpy(out_origin_offsets, hout.data(), sizeof(int64_t) * (n_out + 1));
+                MCHK(hipMemcpyAsync(out_xyz, do_xyz, sizeof(double) * 3 * n_out, hipMemcpyDeviceToHost, st));
+                if (hout[n_out]) {
+                    MCHK(hipMemcpyAsync(out_origin_shot, do_shot, sizeof(int32_t) * hout[n_out], hipMemcpyDeviceToHost, st));
+                    MCHK(hipMemcpyAsync(out_origin_xy, do_xy, sizeof(double) * 2 * hout[n_out], hipMemcpyDeviceToHost, st));
+                }
+            }
+            MCHK(hipStreamSynchronize(st));
+            *out_n_points = n_out;
+            *out_n_origins = hout[n_out];
+            float ms = 0.f, part = 0.f;
+            for (int i = 0; i < 6; i += 2) {
+                if (hipEventElapsedTime(&part, ev[i], ev[i + 1]) == hipSuccess) ms += part;
+            }
+            g_last_ms = ms;
+        }
+    done:;
+    } catch (const std::bad_alloc&) {   // the host buffers; no exception crosses the ABI
+        rc = SFMX_ENOMEM;
+        set_last_error("host allocation failed");
+    }
+    if (device_set && prev >= 0) (void)hipSetDevice(prev);
+    return rc;
+}
+
+}  // extern "C"

@@ -13,5 +13,6 @@ from .matching import (  # noqa: F401
 
 from . import homography, scene, mvs, features, triangulate  # noqa: F401,E402
 from .triangulate import triangulate_matches, triangulate_matches_device, triangulateMatch  # noqa: F401,E402
+from .scene import merge_pointcloud_3d2d  # noqa: F401,E402
 
 __version__ = "0.1.0"

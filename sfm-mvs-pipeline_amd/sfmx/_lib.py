@@ -156,6 +156,12 @@ PROTOTYPES = {
     "sfmx_find_3d2d_last_kernel_ms": (C.c_float, []),
     "sfmx_ba_observations_from_origins": (C.c_int, [_i64p, C.c_int32, _i32p, _P(C.c_double), C.c_int32, _i32p, _i32p,
                                                     _P(C.c_double), _i32p, _i32p, _i32p]),
+    "sfmx_merge_pointcloud_3d2d": (C.c_int, [_P(_vp), _i32p, C.c_int32, _i32p, C.c_int32, _vp, _vp,
+                                             _vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp,
+                                             C.c_double, C.c_double, C.c_int32, C.c_int32, _vp,
+                                             _vp, _vp, _vp, _vp, _vp, _vp, _i32p, _i64p]),
+    "sfmx_merge_pointcloud_last_kernel_ms": (C.c_float, []),
+    "sfmx_merge_pointcloud_last_stats": (C.c_int, [_i64p, _i64p, _i64p]),
     "sfmx_undistort_images": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "sfmx_sift_default_params": (None, [_vp]),
     "sfmx_sift_detect_compute": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int32, C.c_int32, _vp, _vp,
