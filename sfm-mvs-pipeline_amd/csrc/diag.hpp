@@ -10,6 +10,10 @@
 // wrong results exist only in that build.
 #pragma once
 
+// SFMX_SIFT_VARIANT value (diagnostic build) of the list path with the exact int8 screen and the subset
+// pass 2, the product path before the FP6 screen: kept for A/B timing and parity tests.
+constexpr int SIFT_VARIANT_INT8_LISTS = 110;
+
 #ifdef SFMX_DIAG
 #include <cstdlib>
 #define SFMX_DIAG_ENV(name) std::getenv(name)

@@ -5,6 +5,9 @@
 //   SIFT (NORM_L2):  desc8[row][128]  int8   a' = a - 128   (exact: SIFT values are integers 0..255)
 //                    norm [row]       int32  ||a'||^2        (<= 2^21)
 //                    keyc [row]       int32  -(||a'||^2 << 8) + 255 - (row & 255)   (see match_kernels.hip)
+//                    desc6[row][96 B] e2m3   a = u - 32 quantised for the FP6 screen (sift_fp6.hpp: layout, bound)
+//                    keyf [row]       float  -||a||^2 / 2048, the FP6 screen's C operand
+//                    ne   [row]       int2   (||a||^2, ||e||^2), e the quantisation error; per-image maxima in imax
 //                    f32  [row][128]  float  only when an image is not integer-valued (fp32 fallback)
 //   ORB (NORM_HAMMING): desc8[row][32] uint8 (rows padded with zeros)
 // Images are concatenated; each starts at a row offset that is a multiple of

@@ -42,6 +42,7 @@
 #include <cstdlib>
 #include "match_common.hpp"
 #include "diag.hpp"
+#include "sift_fp6.hpp"
 
 namespace sfmx {
 
@@ -106,10 +107,16 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg) {
 // ---------------------------------------------------------------------------
 // prep: float SIFT rows -> int8 a' = a - 128, ||a'||^2, chunk keys, integrality.
 // 32 threads per row (float4 each); pad rows are written as zeros.
-__device__ __forceinline__ void prep_l2_row(const float* __restrict__ src, int r, int rows, int cols,
+// The FP6 screen's per-row operands (sift_fp6.hpp), written by the batched prep beside the int8 ones.
+struct Fp6Rows {
+    uint32_t* desc6;   // [row][24]  packed e2m3 row
+    float* keyf;       // [row]      C operand -|a|^2 / 2048 (pad rows: fp6::PAD_KEY)
+    int2* ne;          // [row]      (|a|^2, |e|^2), a = u - 32
+};
+__device__ __forceinline__ int2 prep_l2_row(const float* __restrict__ src, int r, int rows, int cols,
                                             int8_t* __restrict__ dst, int32_t* __restrict__ norm,
                                             int32_t* __restrict__ keyc, int32_t* __restrict__ keyc2,
-                                            int32_t* __restrict__ nonintegral);
+                                            int32_t* __restrict__ nonintegral, const Fp6Rows* f6 = nullptr);
 __global__ void prep_l2_kernel(const float* __restrict__ src, int rows, int cols, int rows_pad,
                                int8_t* __restrict__ dst, int32_t* __restrict__ norm,
                                int32_t* __restrict__ keyc, int32_t* __restrict__ keyc2,
@@ -123,18 +130,41 @@ constexpr int PREP_ROWS = 64;   // rows per workgroup of the batched prep
 static_assert(ROW_ALIGN % PREP_ROWS == 0 && PREP_ROWS % 8 == 0, "whole 8-row steps, no partial workgroup");
 __global__ void prep_l2_batch_kernel(const PrepImg* __restrict__ tab, int8_t* __restrict__ desc8,
                                      int32_t* __restrict__ norm, int32_t* __restrict__ keyc,
-                                     int32_t* __restrict__ keyc2, int32_t* __restrict__ flags) {
+                                     int32_t* __restrict__ keyc2, int32_t* __restrict__ flags, Fp6Rows f6,
+                                     int32_t* __restrict__ imax) {
     const PrepImg t = tab[blockIdx.y];
+    const Fp6Rows f6i{f6.desc6 + t.row0 * fp6::ROW_WORDS, f6.keyf + t.row0, f6.ne + t.row0};
+    int emax = 0, amax = 0;   // the image's largest |e|^2 and |a|^2 over this workgroup's rows
     // PREP_ROWS rows per workgroup, 8 at a time (rows_pad is a multiple of PREP_ROWS)
     for (int r = blockIdx.x * PREP_ROWS + (threadIdx.x >> 5); r < min((int)(blockIdx.x + 1) * PREP_ROWS, t.rows_pad);
-         r += blockDim.x >> 5)
-        prep_l2_row(t.src, r, t.rows, t.cols, desc8 + t.row0 * SIFT_DIM, norm + t.row0, keyc + t.row0, keyc2 + t.row0,
-                    flags + blockIdx.y);
+         r += blockDim.x >> 5) {
+        const int2 em = prep_l2_row(t.src, r, t.rows, t.cols, desc8 + t.row0 * SIFT_DIM, norm + t.row0, keyc + t.row0,
+                                    keyc2 + t.row0, flags + blockIdx.y, &f6i);
+        emax = max(emax, em.x);
+        amax = max(amax, em.y);
+    }
+    // One pair of atomics per workgroup at most, and only where it raises the image's maximum (imax is zero
+    // before the launch): every image's words share a few cache lines, and unconditional atomics from each
+    // wave serialised there (prep 283 -> 158 us on 50 x 8192 rows with this guard).
+    __shared__ int wmax[2][PREP_ROWS / 8];
+    for (int o = 32; o > 0; o >>= 1) {
+        emax = max(emax, __shfl_xor(emax, o));
+        amax = max(amax, __shfl_xor(amax, o));
+    }
+    if ((threadIdx.x & 63) == 0) { wmax[0][threadIdx.x >> 6] = emax; wmax[1][threadIdx.x >> 6] = amax; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        int v = 0;
+        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) v = max(v, wmax[threadIdx.x][i]);
+        int32_t* p = imax + 2 * blockIdx.y + threadIdx.x;
+        if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
+    }
 }
-__device__ __forceinline__ void prep_l2_row(const float* __restrict__ src, int r, int rows, int cols,
+// -> (|e|^2, |a|^2) of the row's FP6 form (0, 0 for a pad row or without f6).
+__device__ __forceinline__ int2 prep_l2_row(const float* __restrict__ src, int r, int rows, int cols,
                                             int8_t* __restrict__ dst, int32_t* __restrict__ norm,
                                             int32_t* __restrict__ keyc, int32_t* __restrict__ keyc2,
-                                            int32_t* __restrict__ nonintegral) {
+                                            int32_t* __restrict__ nonintegral, const Fp6Rows* f6) {
     const int c4 = threadIdx.x & 31;   // 4 columns each
     int v[4] = {0, 0, 0, 0};
     bool bad = false;
@@ -167,6 +197,31 @@ __device__ __forceinline__ void prep_l2_row(const float* __restrict__ src, int r
         keyc[r] = (r < rows) ? (-(n2 << 8) + 255 - (r & 255)) : INT_MIN;
         keyc2[r] = (r < rows) ? -((n2 + 1) >> 1) : PAD_KEY;     // screening pass: -ceil(nb / 2)
     }
+    if (!f6) return make_int2(0, 0);
+    // FP6 form of u = v + 128: a = u - 32 = v + 96 = SCALE m + e; 4 elements = 24 bits per lane, 8 lanes per
+    // 192-bit fragment, whose word w is cut from the 48 bits of lanes (4 w) / 3 and (4 w) / 3 + 1.
+    // One reduction for both sums: |e|^2 <= 2^13 above sum (v + 128) < 2^15; |a|^2 = n2 + 192 sum v + 128 * 96^2.
+    unsigned chunk = 0;
+    int red = 0;
+    if (r < rows) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int a = v[e] + 128 - fp6::OFFSET, m = fp6::quant_m(a), er = a - fp6::SCALE * m;
+            chunk |= fp6::code_of_m(m) << (6 * e);
+            red += ((er * er) << 16) + v[e] + 128;
+        }
+    }
+    for (int o = 16; o > 0; o >>= 1) red += __shfl_xor(red, o, 32);
+    const int e2 = red >> 16, a2 = r < rows ? n2 + 192 * ((red & 0xFFFF) - 128 * 128) + 128 * 96 * 96 : 0;
+    const int w = c4 & 7, g = c4 >> 3, j0 = min((4 * w) / 3, 6);
+    const unsigned lo = __shfl(chunk, (c4 & ~7) + j0, 32), hi = __shfl(chunk, (c4 & ~7) + j0 + 1, 32);
+    const unsigned word = (unsigned)((((unsigned long long)hi << 24) | lo) >> (w < 6 ? 32 * w - 24 * j0 : 0));
+    if (w < 6) f6->desc6[(int64_t)r * fp6::ROW_WORDS + fp6::word_index(g, w)] = word;
+    if (c4 == 0) {
+        f6->keyf[r] = (r < rows) ? -(float)a2 * (1.0f / 2048.0f) : fp6::PAD_KEY;   // exact: a2 < 2^23
+        f6->ne[r] = make_int2(a2, e2);
+    }
+    return make_int2(e2, a2);
 }
 
 // Copy of the raw float rows for the fp32 fallback (non-integer SIFT values).
@@ -219,7 +274,10 @@ __global__ void prep_hamming_fp4_kernel(const uint8_t* __restrict__ src, int row
 // *work2_n items built by compact_work_kernel; an item's queries are entries
 // [q0, q0 + 512) of its pair's list of unresolved queries (qlist at the pair's
 // dense_base, qcount[pair] entries) written by sift_screen_kernel.
-template <int QT, int WAVES, int MINW, int STAGE, bool MFMA_FIRST, int PROBE = 0, int PIPE = 0, bool GATHER = false>
+// LISTS (with GATHER; the product path behind sift_screen6_kernel): the query's exact top-2 goes to its list
+// slot of `top2` as the two (s << 32) | j keys sift_finish_kernel merges for a mask of other than two bits.
+template <int QT, int WAVES, int MINW, int STAGE, bool MFMA_FIRST, int PROBE = 0, int PIPE = 0, bool GATHER = false,
+          bool LISTS = false>
 __global__ __launch_bounds__(WAVES * 64, MINW)
 void sift_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restrict__ pairs,
                       const ImgDev* __restrict__ imgs, const int8_t* __restrict__ desc8,
@@ -227,7 +285,8 @@ void sift_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restri
                       int32_t* __restrict__ out_idx, float* __restrict__ out_dist,
                       int2* __restrict__ slow_list, int32_t* __restrict__ slow_count, double ratio,
                       const int32_t* __restrict__ qlist = nullptr, const int32_t* __restrict__ qcount = nullptr,
-                      const int32_t* __restrict__ work2_n = nullptr) {
+                      const int32_t* __restrict__ work2_n = nullptr, unsigned long long* __restrict__ top2 = nullptr) {
+    static_assert(!LISTS || GATHER, "the list slots are the gathered entries");
     constexpr int GLDS = STAGE * SIFT_DIM / (WAVES * 64 * 16);   // 16-B LDS-DMA pieces per thread per stage
     static_assert(GLDS * WAVES * 64 * 16 == STAGE * SIFT_DIM, "stage must split into whole 16-B pieces");
     static_assert(256 % STAGE == 0, "stages tile the 256-row key chunk");
@@ -430,6 +489,13 @@ void sift_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restri
     for (int qt = 0; qt < QT; ++qt) {
         const int qi = qrow[qt];
         if (h != 0 || qi < 0) continue;
+        if constexpr (LISTS) {   // (an empty train image forwards nothing; a missing key stays ~0: unsettled)
+            const long long na = norm[L.row0 + qi];
+            const unsigned long long k1 = T1[qt] != INT_MAX ? ((unsigned long long)(na + T1[qt]) << 32) | (unsigned)J1[qt] : ~0ull;
+            const unsigned long long k2 = T2[qt] != INT_MAX ? ((unsigned long long)(na + T2[qt]) << 32) | (unsigned)J2[qt] : ~0ull;
+            *reinterpret_cast<ulonglong2*>(top2 + 2 * (P.dense_base + qbase + qt * 32 + l32)) = make_ulonglong2(k1, k2);
+            continue;
+        }
         const int64_t o = P.dense_base + qi;
         if (nt == 0) { out_idx[o] = -1; out_dist[o] = 0.f; continue; }
         const int64_t na = norm[L.row0 + qi];
@@ -612,7 +678,8 @@ __device__ __forceinline__ int xcd_ticket(int32_t* ticket, int n) {
 // PERSIST (r04, diagnostic build only, see persist_screens): a grid of resident workgroup slots takes work items
 // from a ticket counter in list order (the last partial round of a one-item-per-workgroup grid --
 // C2: 19 600 items on 512 slots, 38.3 rounds -- becomes a ragged end of single items).
-// LISTS (the product path, with SUBSET): nothing goes to the dense per-query arrays.  A rejected query
+// LISTS (with SUBSET; the product path until sift_screen6_kernel, now SIFT_VARIANT_INT8_LISTS): nothing goes to the dense
+// per-query arrays.  A rejected query
 // leaves no trace, a forwarded one is its list entry alone, and its pass-2 state (top2 / slot1) lives at
 // its list slot (dense_base + slot), where sift_subset_kernel<_, true> and sift_finish_kernel find it.
 template <int QT, int WAVES, int MINW, int STAGE, bool SUBSET = false, bool PERSIST = false, bool LISTS = false>
@@ -779,6 +846,153 @@ void sift_screen16_kernel(const WorkItem* __restrict__ work, const PairDev* __re
 }
 
 // ---------------------------------------------------------------------------
+// Screening pass of the product path on the FP6 matrix pipe: v_mfma_scale_f32_16x16x128_f8f6f4 with e2m3
+// operands, one MFMA (K = 128) per 16 x 16 tile, twice the MACs per clock of the int8 screens.  The
+// operands are quantised, so the screen is conservative rather than exact (sift_fp6.hpp: quantiser, key,
+// bound and its proof): it rejects a query only when Lowe's test fails at a lower bound of s1 and an upper
+// bound of s2, and forwards every other one -- a superset of what sift_screen16_kernel forwards -- to the
+// exact pass 2 (sift_knn2_kernel<GATHER, LISTS>), whose results do not depend on which rejected queries
+// were forwarded as well.  The bound is too wide to name the subsets that can hold the two neighbours,
+// so every forwarded query carries the full mask and pass 2 scans every train row.
+//   Loop structure of orb_screen16_kernel: A = 16 train rows (LDS), B = 16 queries (registers), the f32 C
+//   operand is the row's key, v_max3_f32 folds two row blocks into 4 chains per lane (16 row subsets per
+//   query with the other three lanes of the column).
+//   LDS stage: plane A (64 B per row: the first 16 B of each lane group's 24-B fragment) | plane B (32 B
+//   per row: the last 8 B) | keys, filled by 16-B LDS-DMA from the 96-B rows with the swizzle on the
+//   source address (fp6::swz_a / swz_b keep ds_read_b128 / ds_read_b64 conflict-free in their lane groups).
+template <int QT, int WAVES, int MINW, int STAGE>
+__global__ __launch_bounds__(WAVES * 64, MINW)
+void sift_screen6_kernel(const WorkItem* __restrict__ work, const PairDev* __restrict__ pairs,
+                         const ImgDev* __restrict__ imgs, const uint32_t* __restrict__ desc6,
+                         const float* __restrict__ keyf, const int2* __restrict__ ne,
+                         const int32_t* __restrict__ imax,
+                         int32_t* __restrict__ qlist, int32_t* __restrict__ qcount, double ratio,
+                         int32_t* __restrict__ qmask, unsigned long long* __restrict__ top2) {
+    static_assert(QT * WAVES * 16 == 512, "work items are 512 queries");
+    static_assert(WAVES == 4 && STAGE % 128 == 0 && ROW_ALIGN % STAGE == 0, "whole DMA instructions per wave; stages inside the padded rows");
+    constexpr int A_BYTES = STAGE * 64, B_BYTES = STAGE * 32;
+    constexpr int GA = A_BYTES / (WAVES * 64 * 16), GB = B_BYTES / (WAVES * 64 * 16), GK = STAGE / 64;
+    constexpr int BUF_BYTES = A_BYTES + B_BYTES + STAGE * 4;
+    __shared__ __attribute__((aligned(16))) char lds[2 * BUF_BYTES];
+
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
+    const WorkItem w = work[xcd_remap(blockIdx.x, gridDim.x)];
+    const PairDev P = pairs[w.pair];
+    const ImgDev L = imgs[P.left], R = imgs[P.right];
+    const int nq = L.rows, nt = R.rows;
+    const int qbase = w.q0 + wid * (QT * 16);
+
+    // Query fragments (B operand): lane group g's 192 bits of the row (fp6::word_index)
+    i32x8 bq[QT];
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+        const uint32_t* src = desc6 + (L.row0 + qbase + qt * 16 + l16) * fp6::ROW_WORDS;   // rows < rows_pad
+        const i32x4 lo = *reinterpret_cast<const i32x4*>(src + 4 * g);
+        const int2 hi = *reinterpret_cast<const int2*>(src + 16 + 2 * g);
+        bq[qt] = i32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, 0, 0};
+    }
+    float ch[QT][4];
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ch[qt][i] = fp6::KEY_INIT;
+
+    const int nstages = (nt + STAGE - 1) / STAGE;
+    const char* tbase = reinterpret_cast<const char*>(desc6 + R.row0 * fp6::ROW_WORDS);
+    const float* kbase = keyf + R.row0;
+    auto stage = [&](int s, int buf) {
+        char* base = lds + buf * BUF_BYTES;
+#pragma unroll
+        for (int i = 0; i < GA; ++i) {   // plane A: 4 pieces per row
+            const int p = i * WAVES * 64 + threadIdx.x;
+            const int rr = p >> 2, c = (p & 3) ^ fp6::swz_a(rr);
+            const char* gp = tbase + (int64_t)(s * STAGE + rr) * fp6::ROW_BYTES + 16 * c;
+            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gp,
+                                             (LDS_AS void*)(base + (i * WAVES + wid) * 1024), 16, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < GB; ++i) {   // plane B: 2 pieces per row
+            const int p = i * WAVES * 64 + threadIdx.x;
+            const int rr = p >> 1, c = (p & 1) ^ fp6::swz_b(rr);
+            const char* gp = tbase + (int64_t)(s * STAGE + rr) * fp6::ROW_BYTES + 64 + 16 * c;
+            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gp,
+                                             (LDS_AS void*)(base + A_BYTES + (i * WAVES + wid) * 1024), 16, 0, 0);
+        }
+        if (wid < GK)
+            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(kbase + s * STAGE + wid * 64 + lane),
+                                             (LDS_AS void*)(base + A_BYTES + B_BYTES + wid * 256), 4, 0, 0);
+    };
+
+    if (nstages > 0) stage(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int s = 0; s < nstages; ++s) {
+        const int buf = s & 1;
+        if (s + 1 < nstages) stage(s + 1, buf ^ 1);
+        const char* base = lds + buf * BUF_BYTES;
+#pragma unroll
+        for (int t = 0; t < STAGE / 32; ++t) {
+            i32x8 a[2];
+            f32x4 cinit[2];
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int row = t * 32 + b * 16 + l16;
+                const i32x4 lo = *reinterpret_cast<const i32x4*>(base + row * 64 + 16 * (g ^ fp6::swz_a(row)));
+                const int2 hi = *reinterpret_cast<const int2*>(base + A_BYTES + row * 32 +
+                                                               16 * ((g >> 1) ^ fp6::swz_b(row)) + 8 * (g & 1));
+                a[b] = i32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, 0, 0};
+                cinit[b] = *reinterpret_cast<const f32x4*>(base + A_BYTES + B_BYTES + 4 * (t * 32 + b * 16 + 4 * g));
+            }
+#pragma unroll
+            for (int qt = 0; qt < QT; ++qt) {
+                // format code 2 = e2m3 for both operands, unit E8M0 scales
+                const f32x4 acc0 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[0], bq[qt], cinit[0], 2, 2, 0, 0x7f7f7f7f,
+                                                                                    0, 0x7f7f7f7f);
+                const f32x4 acc1 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[1], bq[qt], cinit[1], 2, 2, 0, 0x7f7f7f7f,
+                                                                                    0, 0x7f7f7f7f);
+                // (folding one tile behind, the folds pinned under the next tile's MFMAs, measured slower: DESIGN 5)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) ch[qt][i] = fmaxf(fmaxf(ch[qt][i], acc0[i]), acc1[i]);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+
+    const int emax2 = imax[2 * P.right], amax2 = imax[2 * P.right + 1];
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+        float k1 = fp6::KEY_INIT, k2 = fp6::KEY_INIT;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float v = ch[qt][i];
+            k2 = fmaxf(k2, fminf(k1, v));
+            k1 = fmaxf(k1, v);
+        }
+#pragma unroll
+        for (int o = 16; o <= 32; o <<= 1) {
+            const float p1 = __shfl_xor(k1, o), p2 = __shfl_xor(k2, o);
+            k2 = fmaxf(fminf(k1, p1), fmaxf(k2, p2));
+            k1 = fmaxf(k1, p1);
+        }
+        const int qi = qbase + qt * 16 + l16;
+        if (g != 0 || qi >= nq || nt == 0) continue;   // an empty train image: no neighbour, nothing to forward
+        // straight-line integer arithmetic decides (lowe_select: no bool PHI): the bound is usable with two
+        // train rows in two different subsets, every other query is forwarded
+        const int2 q2 = ne[L.row0 + qi];
+        const int usable = (int)(nt >= 2) & (int)(k2 > fp6::KEY_VALID);
+        const int rej = usable & fp6::certainly_rejected(k1, k2, q2.x, q2.y, emax2, amax2, ratio);
+        if (rej == 0) {
+            const int64_t slot = P.dense_base + atomicAdd(&qcount[w.pair], 1);
+            qlist[slot] = qi;
+            qmask[slot] = 0xFFFF;   // not a two-bit mask: sift_finish_kernel reads the slot's own two keys
+            top2[2 * slot] = ~0ull;   // pass 2 overwrites both (a slot it misses counts as unsettled)
+            top2[2 * slot + 1] = ~0ull;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Pass 2, subset form (SFMX_SIFT_P2 = 10): one workgroup per (pair, row subset r), r = j mod 16.
 // The screen forwarded each unsettled query with the mask of the subsets whose maximum reaches
 // its second-largest subset maximum; only rows of those subsets can be the first or second
@@ -815,7 +1029,7 @@ void sift_screen16_kernel(const WorkItem* __restrict__ work, const PairDev* __re
 // ends on plain stores instead of waiting for a returning atomic.  Every other mask (3+ subsets,
 // or all 16 when the screen's bound was not usable) takes the atomics above.
 //
-// LISTS (the product path): the query's pass-2 state lives at its list slot, dense_base + e, not at
+// LISTS (the list path of SIFT_VARIANT_INT8_LISTS): the query's pass-2 state lives at its list slot, dense_base + e, not at
 // its row: the gather carries e (16 bits, relative to the window) beside the packed row | mode, and
 // sift_finish_kernel walks the same slots in order instead of two scattered 16-B reads per query.
 template <int WAVES, bool LISTS = false>
@@ -1025,11 +1239,13 @@ __global__ void probe_xor80_kernel(uint32_t* __restrict__ p, int64_t n_words) {
     if (i < n_words) p[i] ^= 0x80808080u;
 }
 #endif
+// imax[2 i], imax[2 i + 1]: image i's largest |e|^2 and |a|^2 (zero before the launch).
 hipError_t launch_prep_l2_batch(const PrepImg* tab, int n, int max_rows_pad, int8_t* desc8, int32_t* norm,
-                                int32_t* keyc, int32_t* keyc2, int32_t* flags, hipStream_t st) {
+                                int32_t* keyc, int32_t* keyc2, int32_t* flags, uint32_t* desc6, float* keyf,
+                                int2* ne, int32_t* imax, hipStream_t st) {
     if (n == 0 || max_rows_pad == 0) return hipSuccess;
     prep_l2_batch_kernel<<<dim3((unsigned)((max_rows_pad + PREP_ROWS - 1) / PREP_ROWS), (unsigned)n), 256, 0, st>>>(
-        tab, desc8, norm, keyc, keyc2, flags);
+        tab, desc8, norm, keyc, keyc2, flags, Fp6Rows{desc6, keyf, ne}, imax);
     return hipGetLastError();
 }
 // The per-image integrality flags into pinned, host-coherent memory, then a sequence word with
@@ -2272,7 +2488,8 @@ hipError_t launch_prep_hamming(const uint8_t* src, int rows, int cols, int rows_
 }
 
 // Kernel variants (queries per block = QT * WAVES * 32, must divide ROW_ALIGN).
-// The product library runs only the default two-pass forms (variant 0, subset pass 2);
+// The product library runs only the default two-pass forms (variant 0: the FP6 screen with the exact pass 2
+// over every row for SIFT, the FP4 screen with the subset pass 2 for ORB);
 // the diagnostic build (diag.hpp) selects the others with SFMX_SIFT_VARIANT / SFMX_SIFT_P2,
 // read per run so tests switch paths within one process.
 int sift_variant() {
@@ -2318,13 +2535,28 @@ hipError_t launch_sift_knn2(const WorkItem* work, int n_work, const PairDev* pai
                             int32_t* work2_n, int32_t* out_idx,
                             float* out_dist, int2* slow_list, int32_t* slow_count, double ratio, hipStream_t st,
                             hipEvent_t ev_screen, int32_t* qmask, unsigned long long* top2, unsigned long long* slot1,
-                            bool lists) {
+                            bool lists, const uint32_t* desc6, const float* keyf, const int2* ne, const int32_t* imax) {
     if (n_work == 0) return hipSuccess;
     const int v = sift_variant();
     if (v == 0 || v >= 101) {   // two-pass ratio test: screen every query, exact kernel on the rest
         hipError_t e = hipSuccess;   // qcount and the screen's XCD tickets behind it: zeroed by the caller's one fill
         if (lists) {   // product path: pass-2 state at the list slots; the caller settles with launch_finish_lists
-            if (v != 0 || pass2_variant() != 10 || !qmask || !top2) return hipErrorInvalidValue;
+            if ((v != 0 && v != SIFT_VARIANT_INT8_LISTS) || pass2_variant() != 10 || !qmask || !top2) return hipErrorInvalidValue;
+            if (v == 0) {   // conservative FP6 screen, exact pass 2 over every train row (128-query items)
+                if (!desc6 || !keyf || !ne || !imax) return hipErrorInvalidValue;
+                sift_screen6_kernel<8, 4, 2, 128><<<n_work, 256, 0, st>>>(work, pairs, imgs, desc6, keyf, ne, imax, qlist, qcount,
+                                                                         ratio, qmask, top2);
+                if (ev_screen) {
+                    e = hipEventRecord(ev_screen, st);
+                    if (e != hipSuccess) return e;
+                }
+                compact_work_kernel<7><<<1, 1024, 0, st>>>(porder, n_pairs, qcount, work2, work2_n);
+                sift_knn2_kernel<1, 4, 2, 128, false, 0, 0, true, true><<<n_work << 2, 256, 0, st>>>(   // work2 holds n_work << 2 items
+                    work2, pairs, imgs, desc8, norm, keyc, nullptr, nullptr, nullptr, nullptr, ratio, qlist, qcount, work2_n,
+                    top2);
+                return hipGetLastError();
+            }
+            // SIFT_VARIANT_INT8_LISTS (diagnostic build): the exact int8 screen with subset masks, subset pass 2
             sift_screen16_kernel<8, 4, 2, 64, true, false, true><<<n_work, 256, 0, st>>>(
                 work, pairs, imgs, desc8, norm, keyc2, out_idx, out_dist, qlist, qcount, ratio, qmask, top2);
             if (ev_screen) {

@@ -27,18 +27,21 @@
 
 #include "../../include/sfmx.h"
 #include "match_common.hpp"
+#include "sift_fp6.hpp"
 
 namespace sfmx {
 hipError_t launch_prep_l2(const float*, int, int, int, int8_t*, int32_t*, int32_t*, int32_t*, int32_t*, hipStream_t);
 hipError_t launch_probe_xor80(int8_t*, int64_t, hipStream_t);
 hipError_t launch_publish_flags(const int32_t*, int, int32_t*, unsigned*, unsigned, hipStream_t);
-hipError_t launch_prep_l2_batch(const PrepImg*, int, int, int8_t*, int32_t*, int32_t*, int32_t*, int32_t*, hipStream_t);
+hipError_t launch_prep_l2_batch(const PrepImg*, int, int, int8_t*, int32_t*, int32_t*, int32_t*, int32_t*, uint32_t*, float*,
+                                int2*, int32_t*, hipStream_t);
 hipError_t launch_prep_f32(const float*, int, int, int, float*, hipStream_t);
 hipError_t launch_prep_hamming(const uint8_t*, int, int, int, uint8_t*, hipStream_t);
 hipError_t launch_sift_knn2(const WorkItem*, int, const PairDev*, const ImgDev*, const int8_t*, const int32_t*,
                             const int32_t*, const int32_t*, int32_t*, int32_t*, int, const int32_t*, WorkItem*,
                             int32_t*, int32_t*, float*, int2*, int32_t*, double, hipStream_t, hipEvent_t, int32_t*,
-                            unsigned long long*, unsigned long long*, bool);
+                            unsigned long long*, unsigned long long*, bool, const uint32_t*, const float*, const int2*,
+                            const int32_t*);
 hipError_t launch_finish_lists(const PairRec*, int, const int32_t*, const int32_t*, const int32_t*, unsigned long long*,
                                const unsigned long long*, int2*, int32_t*, const int8_t*, const int32_t*, const int32_t*,
                                const float*, double, int, int, int, int, int64_t*, int32_t*, int64_t*, DMatchDev*, int32_t*,
@@ -167,6 +170,10 @@ struct sfmx_matcher {
     int max_rows = 0;
     bool any_nonintegral = false;
     DevBuf raw, desc8, normv, keyc, keyc2, f32, flags, imgs_d;
+    // FP6 screen (sift_fp6.hpp): packed e2m3 rows, f32 C-operand keys, (|u - 32|^2, |e|^2) per row; the
+    // per-image maxima of |e|^2 and |u - 32|^2 live behind the integrality flags (imax: one fill for both)
+    DevBuf desc6, keyf, ne;
+    DevView imax;
     // run state
     int n_pairs = 0;
     int64_t dense_total = 0;
@@ -281,13 +288,20 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
     const int row_bytes = (norm == SFMX_NORM_L2 || m->orb_fp4) ? SIFT_DIM : ORB_BYTES;
     int rc;
     if ((rc = m->desc8.ensure((size_t)row * row_bytes))) return rc;
-    if ((rc = m->flags.ensure(sizeof(int32_t) * align_up(std::max(n, 1), 64)))) return rc;
+    const int64_t n_flags = align_up(std::max(n, 1), 64);   // flags[n_flags] | imax[2 n_flags]
+    if ((rc = m->flags.ensure(sizeof(int32_t) * 3 * n_flags))) return rc;
+    m->imax.p = m->flags.as<int32_t>() + n_flags;
     if ((rc = m->imgs_d.ensure(sizeof(ImgDev) * std::max(n, 1)))) return rc;
     if (norm == SFMX_NORM_L2 && (rc = m->normv.ensure((size_t)row * 4))) return rc;
     if ((norm == SFMX_NORM_L2 || m->orb_fp4) && (rc = m->keyc.ensure((size_t)row * 4))) return rc;
     if (norm == SFMX_NORM_L2 && (rc = m->keyc2.ensure((size_t)row * 4))) return rc;
+    if (norm == SFMX_NORM_L2) {
+        if ((rc = m->desc6.ensure((size_t)row * fp6::ROW_BYTES))) return rc;
+        if ((rc = m->keyf.ensure((size_t)row * 4))) return rc;
+        if ((rc = m->ne.ensure((size_t)row * sizeof(int2)))) return rc;
+    }
     if (!device_src && (rc = m->raw.ensure((size_t)raw_bytes))) return rc;
-    HIPCHK(hipMemsetAsync(m->flags.p, 0, sizeof(int32_t) * align_up(std::max(n, 1), 64), st));   // whole 256-B units: one dispatch
+    HIPCHK(hipMemsetAsync(m->flags.p, 0, sizeof(int32_t) * 3 * n_flags, st));   // whole 256-B units: one dispatch
     std::vector<const void*> src(n);
     for (int i = 0; i < n; ++i) {
         const int64_t esz = norm == SFMX_NORM_L2 ? 4 : 1;
@@ -311,7 +325,8 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
         HIPCHK(hipMemcpyAsync(m->prep_tab.p, tab, sizeof(PrepImg) * n, hipMemcpyHostToDevice, st));
         if ((rc = m->stage_prep.copied(st))) return rc;
         HIPCHK(launch_prep_l2_batch(m->prep_tab.as<PrepImg>(), n, max_pad, m->desc8.as<int8_t>(), m->normv.as<int32_t>(),
-                                    m->keyc.as<int32_t>(), m->keyc2.as<int32_t>(), m->flags.as<int32_t>(), st));
+                                    m->keyc.as<int32_t>(), m->keyc2.as<int32_t>(), m->flags.as<int32_t>(),
+                                    m->desc6.as<uint32_t>(), m->keyf.as<float>(), m->ne.as<int2>(), m->imax.as<int32_t>(), st));
     }
     for (int i = 0; i < n && norm != SFMX_NORM_L2; ++i) {
         const ImgDev& d = m->imgs[i];
@@ -400,9 +415,11 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
     std::vector<int64_t> img_key(2 * (size_t)m->n_imgs);
     for (int i = 0; i < m->n_imgs; ++i) { img_key[2 * i] = m->imgs[i].rows; img_key[2 * i + 1] = m->imgs[i].integral; }
     const int nb_want = match_batches();
-    // List path: the product SIFT path (default screen, subset pass 2, one batch).  Every diagnostic
-    // variant and ORB keep the dense per-query arrays; fp32-fallback pairs of a list run do too, per pair.
-    const bool lists = m->norm == SFMX_NORM_L2 && variant_key == 0 && pass2_variant() == 10 && nb_want == 1 &&
+    // List path: the product SIFT path (FP6 screen, exact pass 2 over every row, one batch) and its int8
+    // predecessor (SIFT_VARIANT_INT8_LISTS: int8 screen, subset pass 2).  Every other diagnostic variant and
+    // ORB keep the dense per-query arrays; fp32-fallback pairs of a list run do too, per pair.
+    const bool lists = m->norm == SFMX_NORM_L2 && (variant_key == 0 || variant_key == SIFT_VARIANT_INT8_LISTS) &&
+                       pass2_variant() == 10 && nb_want == 1 &&
                        !persist_screens();
     const bool reuse = m->plan_valid && m->plan_variant == variant_key && m->plan_imgs == img_key && m->plan_nb == nb_want &&
                        m->plan_lists == lists &&
@@ -573,7 +590,8 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
                                 m->dense_dist.as<float>(), m->slow_list.as<int2>(), m->slow_count.as<int32_t>(), ratio, st,
                                 m->ev[3], m->qmask.as<int32_t>(), m->top2.as<unsigned long long>(),
                                 m->out.as<unsigned long long>(),   // pass 2's second slot: `out` is idle until assembly
-                                m->plan_lists));
+                                m->plan_lists, m->desc6.as<uint32_t>(), m->keyf.as<float>(), m->ne.as<int2>(),
+                                m->imax.as<int32_t>()));
         if (!m->plan_lists) {
             HIPCHK(hipEventRecord(m->ev[1], st));
             HIPCHK(launch_sift_slow(m->slow_list.as<int2>(), m->slow_count.as<int32_t>(), P, I, m->desc8.as<int8_t>(),
@@ -766,7 +784,7 @@ int sfmx_matcher_destroy(sfmx_matcher* m) {
         m->stage_flags.release();
         if (m->hflags) (void)hipHostFree(m->hflags);
         m->hflags = nullptr;
-        DevBuf* bufs[] = {&m->raw, &m->desc8, &m->normv, &m->keyc, &m->keyc2, &m->qlist, &m->qcount, &m->porder, &m->work2, &m->work2_n, &m->f32, &m->flags, &m->imgs_d, &m->pairs_d, &m->prep_tab,
+        DevBuf* bufs[] = {&m->raw, &m->desc8, &m->normv, &m->keyc, &m->keyc2, &m->desc6, &m->keyf, &m->ne, &m->qlist, &m->qcount, &m->porder, &m->work2, &m->work2_n, &m->f32, &m->flags, &m->imgs_d, &m->pairs_d, &m->prep_tab,
                           &m->work_d, &m->work32_d, &m->dense_idx, &m->dense_dist, &m->slow_list,
                           &m->counts, &m->keep, &m->offsets, &m->out, &m->qmask, &m->top2, &m->recs};
         for (DevBuf* b : bufs) b->release();
