@@ -13,6 +13,9 @@
 // SFMX_SIFT_VARIANT value (diagnostic build) of the list path with the exact int8 screen and the subset
 // pass 2, the product path before the FP6 screen: kept for A/B timing and parity tests.
 constexpr int SIFT_VARIANT_INT8_LISTS = 110;
+// SFMX_SIFT_VARIANT value (diagnostic build) of the list path with the FP6 screen and the full-row pass 2
+// for every forwarded query, the product path before the one-subset certificate: kept for the same uses.
+constexpr int SIFT_VARIANT_FP6_FULL = 111;
 
 #ifdef SFMX_DIAG
 #include <cstdlib>

@@ -30,6 +30,16 @@ constexpr int ORB_BYTES = 32;
 // s equals ranking on sqrtf(s) bits.
 constexpr int64_t SQRT_SAFE = 1 << 22;
 
+// A run's zeroed arena of int32 (one fill): qcount[n_pairs] | the persistent screens' 8 XCD tickets |
+// slow_count | unsettled | qcount2[n_pairs], the per-pair count of forwarded queries on the full-row route
+// of the FP6 product path (sift_screen6_kernel).
+constexpr int ARENA_FIXED = 8 + 2;
+inline int arena_qcount2(int n_pairs) { return n_pairs + ARENA_FIXED; }
+inline int arena_words(int n_pairs) { return 2 * n_pairs + ARENA_FIXED; }
+// qmask of a forwarded query of the FP6 product path that is not certified for one subset: no subset bit
+// (sift_subset_kernel does not gather it) and not two bits (sift_finish_kernel reads the slot's own two keys).
+constexpr int32_t QMASK_FULL_ROUTE = 1 << 16;
+
 struct ImgDev {
     int32_t rows;       // real descriptor rows (Nq or Nt)
     int32_t rows_pad;   // multiple of ROW_ALIGN

@@ -276,8 +276,10 @@ __global__ void prep_hamming_fp4_kernel(const uint8_t* __restrict__ src, int row
 // dense_base, qcount[pair] entries) written by sift_screen_kernel.
 // LISTS (with GATHER; the product path behind sift_screen6_kernel): the query's exact top-2 goes to its list
 // slot of `top2` as the two (s << 32) | j keys sift_finish_kernel merges for a mask of other than two bits.
+// VIA (with LISTS): the item's entries are those of the pair's second list (`qcount` = its counters): entry
+// e names the list slot `via[dense_base + e]`, whose query is gathered and whose two keys are written.
 template <int QT, int WAVES, int MINW, int STAGE, bool MFMA_FIRST, int PROBE = 0, int PIPE = 0, bool GATHER = false,
-          bool LISTS = false>
+          bool LISTS = false, bool VIA = false>
 __global__ __launch_bounds__(WAVES * 64, MINW)
 void sift_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restrict__ pairs,
                       const ImgDev* __restrict__ imgs, const int8_t* __restrict__ desc8,
@@ -285,8 +287,10 @@ void sift_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restri
                       int32_t* __restrict__ out_idx, float* __restrict__ out_dist,
                       int2* __restrict__ slow_list, int32_t* __restrict__ slow_count, double ratio,
                       const int32_t* __restrict__ qlist = nullptr, const int32_t* __restrict__ qcount = nullptr,
-                      const int32_t* __restrict__ work2_n = nullptr, unsigned long long* __restrict__ top2 = nullptr) {
+                      const int32_t* __restrict__ work2_n = nullptr, unsigned long long* __restrict__ top2 = nullptr,
+                      const int32_t* __restrict__ via = nullptr) {
     static_assert(!LISTS || GATHER, "the list slots are the gathered entries");
+    static_assert(!VIA || LISTS, "the second list names list slots");
     constexpr int GLDS = STAGE * SIFT_DIM / (WAVES * 64 * 16);   // 16-B LDS-DMA pieces per thread per stage
     static_assert(GLDS * WAVES * 64 * 16 == STAGE * SIFT_DIM, "stage must split into whole 16-B pieces");
     static_assert(256 % STAGE == 0, "stages tile the 256-row key chunk");
@@ -307,12 +311,15 @@ void sift_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restri
     const int nq = L.rows, nt = R.rows;
     const int qbase = w.q0 + wid * (QT * 32);
     int qrow[QT];                     // query row of this lane's column in each query tile (-1: none)
+    int qslot[QT];                    // LISTS: its list slot
     if constexpr (GATHER) {
         const int cnt = qcount[w.pair];
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             const int e = qbase + qt * 32 + l32;
-            qrow[qt] = e < cnt ? qlist[P.dense_base + e] : -1;
+            qslot[qt] = e;
+            if constexpr (VIA) qslot[qt] = e < cnt ? via[P.dense_base + e] : 0;
+            qrow[qt] = e < cnt ? qlist[P.dense_base + qslot[qt]] : -1;
         }
     } else {
 #pragma unroll
@@ -493,7 +500,7 @@ void sift_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restri
             const long long na = norm[L.row0 + qi];
             const unsigned long long k1 = T1[qt] != INT_MAX ? ((unsigned long long)(na + T1[qt]) << 32) | (unsigned)J1[qt] : ~0ull;
             const unsigned long long k2 = T2[qt] != INT_MAX ? ((unsigned long long)(na + T2[qt]) << 32) | (unsigned)J2[qt] : ~0ull;
-            *reinterpret_cast<ulonglong2*>(top2 + 2 * (P.dense_base + qbase + qt * 32 + l32)) = make_ulonglong2(k1, k2);
+            *reinterpret_cast<ulonglong2*>(top2 + 2 * (P.dense_base + qslot[qt])) = make_ulonglong2(k1, k2);
             continue;
         }
         const int64_t o = P.dense_base + qi;
@@ -852,22 +859,29 @@ void sift_screen16_kernel(const WorkItem* __restrict__ work, const PairDev* __re
 // bound and its proof): it rejects a query only when Lowe's test fails at a lower bound of s1 and an upper
 // bound of s2, and forwards every other one -- a superset of what sift_screen16_kernel forwards -- to the
 // exact pass 2 (sift_knn2_kernel<GATHER, LISTS>), whose results do not depend on which rejected queries
-// were forwarded as well.  The bound is too wide to name the subsets that can hold the two neighbours,
-// so every forwarded query carries the full mask and pass 2 scans every train row.
+// were forwarded as well.  The bound is too wide to name the subsets that can hold the second neighbour,
+// but for most forwarded queries it does name the subset of the first one and shows that no row outside
+// it can decide Lowe's test (fp6::certified).  CERT: such a query gets the one-bit mask of that subset,
+// and the exact top-2 of the subset alone settles it (sift_subset_kernel<_, true>, sift_finish_kernel);
+// every other forwarded query gets QMASK_FULL_ROUTE and its slot is appended to the pair's second list
+// (`qlist2`, counted in `qcount2`), which the full-row pass 2 gathers through (sift_knn2_kernel<VIA>).
+// Without CERT (SIFT_VARIANT_FP6_FULL) every forwarded query carries the full mask and pass 2 scans
+// every train row for it.
 //   Loop structure of orb_screen16_kernel: A = 16 train rows (LDS), B = 16 queries (registers), the f32 C
 //   operand is the row's key, v_max3_f32 folds two row blocks into 4 chains per lane (16 row subsets per
 //   query with the other three lanes of the column).
 //   LDS stage: plane A (64 B per row: the first 16 B of each lane group's 24-B fragment) | plane B (32 B
 //   per row: the last 8 B) | keys, filled by 16-B LDS-DMA from the 96-B rows with the swizzle on the
 //   source address (fp6::swz_a / swz_b keep ds_read_b128 / ds_read_b64 conflict-free in their lane groups).
-template <int QT, int WAVES, int MINW, int STAGE>
+template <int QT, int WAVES, int MINW, int STAGE, bool CERT>
 __global__ __launch_bounds__(WAVES * 64, MINW)
 void sift_screen6_kernel(const WorkItem* __restrict__ work, const PairDev* __restrict__ pairs,
                          const ImgDev* __restrict__ imgs, const uint32_t* __restrict__ desc6,
                          const float* __restrict__ keyf, const int2* __restrict__ ne,
                          const int32_t* __restrict__ imax,
                          int32_t* __restrict__ qlist, int32_t* __restrict__ qcount, double ratio,
-                         int32_t* __restrict__ qmask, unsigned long long* __restrict__ top2) {
+                         int32_t* __restrict__ qmask, unsigned long long* __restrict__ top2,
+                         int32_t* __restrict__ qlist2, int32_t* __restrict__ qcount2) {
     static_assert(QT * WAVES * 16 == 512, "work items are 512 queries");
     static_assert(WAVES == 4 && STAGE % 128 == 0 && ROW_ALIGN % STAGE == 0, "whole DMA instructions per wave; stages inside the padded rows");
     constexpr int A_BYTES = STAGE * 64, B_BYTES = STAGE * 32;
@@ -963,15 +977,21 @@ void sift_screen6_kernel(const WorkItem* __restrict__ work, const PairDev* __res
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
         float k1 = fp6::KEY_INIT, k2 = fp6::KEY_INIT;
+        int r1 = 4 * g;   // the row subset of k1: chain i of lane group g holds rows j = 4 g + i (mod 16)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float v = ch[qt][i];
+            if constexpr (CERT) r1 = v > k1 ? 4 * g + i : r1;
             k2 = fmaxf(k2, fminf(k1, v));
             k1 = fmaxf(k1, v);
         }
 #pragma unroll
         for (int o = 16; o <= 32; o <<= 1) {
             const float p1 = __shfl_xor(k1, o), p2 = __shfl_xor(k2, o);
+            if constexpr (CERT) {   // (equal maxima: either subset; k1 == k2 is never certified)
+                const int pr = __shfl_xor(r1, o);
+                r1 = p1 > k1 ? pr : r1;
+            }
             k2 = fmaxf(fminf(k1, p1), fmaxf(k2, p2));
             k1 = fmaxf(k1, p1);
         }
@@ -985,7 +1005,13 @@ void sift_screen6_kernel(const WorkItem* __restrict__ work, const PairDev* __res
         if (rej == 0) {
             const int64_t slot = P.dense_base + atomicAdd(&qcount[w.pair], 1);
             qlist[slot] = qi;
-            qmask[slot] = 0xFFFF;   // not a two-bit mask: sift_finish_kernel reads the slot's own two keys
+            if constexpr (CERT) {
+                const int cert = fp6::certified(k1, k2, r1, nt, q2.x, q2.y, emax2, amax2, ratio);
+                qmask[slot] = cert ? 1 << r1 : QMASK_FULL_ROUTE;
+                if (!cert) qlist2[P.dense_base + atomicAdd(&qcount2[w.pair], 1)] = (int32_t)(slot - P.dense_base);
+            } else {
+                qmask[slot] = 0xFFFF;   // not a two-bit mask: sift_finish_kernel reads the slot's own two keys
+            }
             top2[2 * slot] = ~0ull;   // pass 2 overwrites both (a slot it misses counts as unsettled)
             top2[2 * slot + 1] = ~0ull;
         }
@@ -1038,7 +1064,8 @@ void sift_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restr
                         const int8_t* __restrict__ desc8, const int32_t* __restrict__ norm,
                         const int32_t* __restrict__ qlist, const int32_t* __restrict__ qmask,
                         const int32_t* __restrict__ qcount, const int32_t* __restrict__ porder,
-                        unsigned long long* __restrict__ top2, unsigned long long* __restrict__ slot1) {
+                        unsigned long long* __restrict__ top2, unsigned long long* __restrict__ slot1,
+                        const int32_t* __restrict__ qcount2 = nullptr, int ride = 0) {
     constexpr int CH = 256;                   // rows per LDS chunk
     constexpr int QC = WAVES * 32;            // queries per tile group (one 32-query tile per wave)
     constexpr int WIN = 1024;                 // forwarded-query window scanned per round
@@ -1065,6 +1092,9 @@ void sift_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restr
     if (cnt == 0 || r >= nt) return;
     const int32_t* qls = qlist + P.dense_base;
     const int32_t* qms = qmask + P.dense_base;
+    // FP6 product path: a pair with at most `ride` queries on the full-row route gets no full-row item
+    // (compact_work_kernel); every subset's workgroup takes them as if their mask had all 16 bits
+    const bool riders = LISTS && qcount2 != nullptr && qcount2[pi] <= ride;
 
     // Chunk c0's rows (XOR-swizzled 16-B pieces; rows past the subset's end are clamped to the
     // chunk's first row, so every address lies in the image's padded rows) -> LDS by DMA;
@@ -1089,8 +1119,11 @@ void sift_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restr
         if (tid == 0) s_n = 0;
         __syncthreads();
         for (int e = e0 + tid; e < min(cnt, e0 + WIN); e += WAVES * 64) {
-            const int mk = qms[e];
+            int mk = qms[e];
+            if constexpr (LISTS) mk = riders && mk == QMASK_FULL_ROUTE ? 0xFFFF : mk;
             if ((mk >> r) & 1) {   // query row (< 2^18) | merge mode << 20: 0 atomics, 1 / 2 the lower / upper of two subsets
+                // (a one-bit mask, the FP6 screen's certified subset, takes the atomics too: its single writer
+                // could store plainly, which measured no faster)
                 const int mode = __popc(mk) == 2 ? ((mk & ((1 << r) - 1)) ? 2 : 1) : 0;
                 const int at = atomicAdd(&s_n, 1);
                 ql[at] = qls[e] | (mode << 20);
@@ -1275,15 +1308,17 @@ hipError_t launch_probe_xor80(int8_t* p, int64_t bytes, hipStream_t st) {
 // Pass-2 work list: ceil(qcount[p] / 512) items per pair, pairs in the host's
 // order (sorted by train image, so XCD-contiguous items share train rows).
 // One 1024-thread block; each thread owns a contiguous run of pairs.
+// A pair with at most `ride` queries gets no item (its queries ride the subset kernel; 0: every pair with a query).
 template <int ISH>   // queries per pass-2 item = 1 << ISH
 __global__ __launch_bounds__(1024)
 void compact_work_kernel(const int32_t* __restrict__ porder, int n_pairs, const int32_t* __restrict__ qcount,
-                         WorkItem* __restrict__ work2, int32_t* __restrict__ work2_n) {
+                         WorkItem* __restrict__ work2, int32_t* __restrict__ work2_n, int ride = 0) {
     __shared__ int wsum[16];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int per = (n_pairs + 1023) / 1024, p0 = min(tid * per, n_pairs), p1 = min(p0 + per, n_pairs);
     int mine = 0;
-    for (int i = p0; i < p1; ++i) mine += (qcount[porder[i]] + (1 << ISH) - 1) >> ISH;
+    auto items = [&](int c) { return c > ride ? (c + (1 << ISH) - 1) >> ISH : 0; };
+    for (int i = p0; i < p1; ++i) mine += items(qcount[porder[i]]);
     int incl = mine;                                  // inclusive scan: wave, then across waves
     for (int o = 1; o < 64; o <<= 1) {
         const int v = __shfl_up(incl, o);
@@ -1295,7 +1330,7 @@ void compact_work_kernel(const int32_t* __restrict__ porder, int n_pairs, const 
     for (int i = 0; i < wv; ++i) base += wsum[i];
     int at = base + incl - mine;
     for (int i = p0; i < p1; ++i) {
-        const int p = porder[i], n = (qcount[p] + (1 << ISH) - 1) >> ISH;
+        const int p = porder[i], n = items(qcount[p]);
         for (int k = 0; k < n; ++k) work2[at++] = WorkItem{p, k << ISH};
     }
     if (tid == 1023) *work2_n = base + incl;
@@ -2297,7 +2332,8 @@ void sift_finish_kernel(const PairRec* __restrict__ recs, const int32_t* __restr
     for (int e = tid; e < cnt; e += 1024) {
         const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(t2 + 2 * e);
         unsigned long long b0 = a.x, b1 = a.y;
-        if (__popc(qms[e]) == 2) {   // two subsets, one 16-B word each: merge the two top-2
+        const int mk = qms[e];
+        if (__popc(mk) == 2) {   // two subsets, one 16-B word each: merge the two top-2
             const ulonglong2 c = *reinterpret_cast<const ulonglong2*>(s1p + 2 * e);
             const unsigned long long lo = b0 < c.x ? b0 : c.x, hi = b0 < c.x ? c.x : b0, m2 = b1 < c.y ? b1 : c.y;
             b0 = lo;
@@ -2308,7 +2344,12 @@ void sift_finish_kernel(const PairRec* __restrict__ recs, const int32_t* __restr
         if (b0 == ~0ull || (nt >= 2 && b1 == ~0ull)) {
             bad += nt != 0;   // pass 2 left a flagged subset unscanned
         } else {
-            const int64_t s1 = (int64_t)(b0 >> 32), s2 = (int64_t)(b1 >> 32);
+            const int64_t s1 = (int64_t)(b0 >> 32);
+            int64_t s2 = (int64_t)(b1 >> 32);
+            // one bit (a subset bit): certified by fp6::certified, (b0, b1) the exact top-2 of that subset alone.
+            // Some row outside it has s in [lo, hi], hi < SQRT_SAFE, and Lowe's test passes at every s2 >= lo:
+            // at the true s2 = min(b1's, s_other) it fails exactly when it fails at b1's clamped below SQRT_SAFE.
+            if (__popc(mk) == 1 && mk < QMASK_FULL_ROUTE) s2 = s2 < SQRT_SAFE ? s2 : SQRT_SAFE - 1;
             if (nt >= 2 && s2 >= SQRT_SAFE) {
                 sl[atomicAdd(&s_slow, 1)] = make_int2(e, qls[e]);
                 continue;
@@ -2489,7 +2530,8 @@ hipError_t launch_prep_hamming(const uint8_t* src, int rows, int cols, int rows_
 
 // Kernel variants (queries per block = QT * WAVES * 32, must divide ROW_ALIGN).
 // The product library runs only the default two-pass forms (variant 0: the FP6 screen with the exact pass 2
-// over every row for SIFT, the FP4 screen with the subset pass 2 for ORB);
+// over the certified row subset, or over every row where there is none, for SIFT; the FP4 screen with the
+// subset pass 2 for ORB);
 // the diagnostic build (diag.hpp) selects the others with SFMX_SIFT_VARIANT / SFMX_SIFT_P2,
 // read per run so tests switch paths within one process.
 int sift_variant() {
@@ -2504,6 +2546,9 @@ int pass2_variant() {   // 10 = subset pass 2 (default), else the full-row GATHE
     const char* e = SFMX_DIAG_ENV("SFMX_SIFT_P2");   // with that item size (0 / 2 = 128 queries)
     return e ? atoi(e) : 10;
 }
+// FP6 product path: the most full-route queries of a pair that ride the subset kernel (16 visits and the
+// atomic merge each) in place of one nearly empty 128-query full-row item (measured).
+constexpr int SIFT_RIDE_MAX = 32;
 int sift_block_queries(int v) { return v == 2 || v == 4 || v == 23 ? 256 : 512; }
 
 #define SIFT_LAUNCH(QT, W, MINW, ST, MF, ...)                                                             \
@@ -2541,11 +2586,33 @@ hipError_t launch_sift_knn2(const WorkItem* work, int n_work, const PairDev* pai
     if (v == 0 || v >= 101) {   // two-pass ratio test: screen every query, exact kernel on the rest
         hipError_t e = hipSuccess;   // qcount and the screen's XCD tickets behind it: zeroed by the caller's one fill
         if (lists) {   // product path: pass-2 state at the list slots; the caller settles with launch_finish_lists
-            if ((v != 0 && v != SIFT_VARIANT_INT8_LISTS) || pass2_variant() != 10 || !qmask || !top2) return hipErrorInvalidValue;
-            if (v == 0) {   // conservative FP6 screen, exact pass 2 over every train row (128-query items)
+            if ((v != 0 && v != SIFT_VARIANT_INT8_LISTS && v != SIFT_VARIANT_FP6_FULL) || pass2_variant() != 10 || !qmask || !top2)
+                return hipErrorInvalidValue;
+            if (v == 0) {
+                // conservative FP6 screen; exact pass 2 over the one certified row subset (one workgroup per
+                // pair and subset), and over every train row for the queries of the second list (128-query
+                // items).  The second list sits in `slot1`, idle here: no mask of this path has two bits.
+                if (!desc6 || !keyf || !ne || !imax || !slot1) return hipErrorInvalidValue;
+                int32_t* qlist2 = reinterpret_cast<int32_t*>(slot1);
+                int32_t* qcount2 = qcount + arena_qcount2(n_pairs);
+                sift_screen6_kernel<8, 4, 2, 128, true><<<n_work, 256, 0, st>>>(work, pairs, imgs, desc6, keyf, ne, imax, qlist,
+                                                                               qcount, ratio, qmask, top2, qlist2, qcount2);
+                if (ev_screen) {
+                    e = hipEventRecord(ev_screen, st);
+                    if (e != hipSuccess) return e;
+                }
+                sift_subset_kernel<4, true><<<n_pairs * 16, 256, 0, st>>>(pairs, imgs, desc8, norm, qlist, qmask, qcount, porder,
+                                                                          top2, slot1, qcount2, SIFT_RIDE_MAX);
+                compact_work_kernel<7><<<1, 1024, 0, st>>>(porder, n_pairs, qcount2, work2, work2_n, SIFT_RIDE_MAX);
+                sift_knn2_kernel<1, 4, 2, 128, false, 0, 0, true, true, true><<<n_work << 2, 256, 0, st>>>(   // work2 holds n_work << 2 items
+                    work2, pairs, imgs, desc8, norm, keyc, nullptr, nullptr, nullptr, nullptr, ratio, qlist, qcount2, work2_n,
+                    top2, qlist2);
+                return hipGetLastError();
+            }
+            if (v == SIFT_VARIANT_FP6_FULL) {   // (diagnostic build) FP6 screen, exact pass 2 over every train row for every forwarded query
                 if (!desc6 || !keyf || !ne || !imax) return hipErrorInvalidValue;
-                sift_screen6_kernel<8, 4, 2, 128><<<n_work, 256, 0, st>>>(work, pairs, imgs, desc6, keyf, ne, imax, qlist, qcount,
-                                                                         ratio, qmask, top2);
+                sift_screen6_kernel<8, 4, 2, 128, false><<<n_work, 256, 0, st>>>(work, pairs, imgs, desc6, keyf, ne, imax, qlist,
+                                                                                qcount, ratio, qmask, top2, nullptr, nullptr);
                 if (ev_screen) {
                     e = hipEventRecord(ev_screen, st);
                     if (e != hipSuccess) return e;

@@ -181,7 +181,7 @@ struct sfmx_matcher {
     DevBuf pairs_d, work_d, work32_d, dense_idx, dense_dist, slow_list, counts, keep, offsets, out;
     DevBuf qlist, qcount;   // two-pass SIFT path: per pair, the queries the screening pass could not settle
     // One zeroed arena per run, a single fill: qcount[n_pairs] | the persistent screens' 8 XCD tickets |
-    // slow_count | unsettled (views into qcount's allocation, set by every run)
+    // slow_count | unsettled | qcount2[n_pairs] (match_common.hpp; views into qcount's allocation, set by every run)
     DevView slow_count;              // int32: length of slow_list
     DevBuf qmask, top2;     // subset pass 2: per forwarded query its row-subset mask; per query the merged top-2 keys
     DevBuf porder, work2, work2_n;   // pair order (by train image) and the compacted pass-2 work list
@@ -415,10 +415,12 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
     std::vector<int64_t> img_key(2 * (size_t)m->n_imgs);
     for (int i = 0; i < m->n_imgs; ++i) { img_key[2 * i] = m->imgs[i].rows; img_key[2 * i + 1] = m->imgs[i].integral; }
     const int nb_want = match_batches();
-    // List path: the product SIFT path (FP6 screen, exact pass 2 over every row, one batch) and its int8
-    // predecessor (SIFT_VARIANT_INT8_LISTS: int8 screen, subset pass 2).  Every other diagnostic variant and
+    // List path: the product SIFT path (FP6 screen, exact pass 2 over the certified subset or every row, one
+    // batch) and its predecessors (SIFT_VARIANT_FP6_FULL: every row for every forwarded query;
+    // SIFT_VARIANT_INT8_LISTS: int8 screen, subset pass 2).  Every other diagnostic variant and
     // ORB keep the dense per-query arrays; fp32-fallback pairs of a list run do too, per pair.
-    const bool lists = m->norm == SFMX_NORM_L2 && (variant_key == 0 || variant_key == SIFT_VARIANT_INT8_LISTS) &&
+    const bool lists = m->norm == SFMX_NORM_L2 &&
+                       (variant_key == 0 || variant_key == SIFT_VARIANT_INT8_LISTS || variant_key == SIFT_VARIANT_FP6_FULL) &&
                        pass2_variant() == 10 && nb_want == 1 &&
                        !persist_screens();
     const bool reuse = m->plan_valid && m->plan_variant == variant_key && m->plan_imgs == img_key && m->plan_nb == nb_want &&
@@ -471,7 +473,7 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
             if ((rc = m->qmask.ensure(sizeof(int32_t) * std::max<int64_t>(dense, 1)))) return rc;
             if ((rc = m->top2.ensure(2 * sizeof(uint64_t) * std::max<int64_t>(dense, 1)))) return rc;
         }
-        if ((rc = m->qcount.ensure(sizeof(int32_t) * align_up(n_pairs + 8 + 2, 64)))) return rc;   // the run's zeroed arena (see qcount)
+        if ((rc = m->qcount.ensure(sizeof(int32_t) * align_up(arena_words(n_pairs), 64)))) return rc;   // the run's zeroed arena (see qcount)
         m->slow_count.p = m->unsettled.p = nullptr;   // views of the old allocation; set again below
         if ((rc = m->porder.ensure(sizeof(int32_t) * std::max(n_pairs, 1)))) return rc;
         if ((rc = m->work2.ensure(sizeof(WorkItem) * std::max<size_t>(4 * work.size(), 1)))) return rc;   // pass-2 items >= 128 queries
@@ -540,7 +542,7 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
     m->slow_count.p = m->qcount.as<int32_t>() + n_pairs + 8;
     m->unsettled.p = m->qcount.as<int32_t>() + n_pairs + 9;
     // the run's only fill; whole 256-B units, which the runtime clears in one dispatch (no unaligned tail)
-    HIPCHK(hipMemsetAsync(m->qcount.p, 0, sizeof(int32_t) * align_up(n_pairs + 8 + 2, 64), st));
+    HIPCHK(hipMemsetAsync(m->qcount.p, 0, sizeof(int32_t) * align_up(arena_words(n_pairs), 64), st));
     HIPCHK(hipEventRecord(m->ev[0], st));
     HIPCHK(hipEventRecord(m->ev[3], st));   // re-recorded after pass 1 by the two-pass launchers
     // Pairs with an empty left image have no work item; pairs with an empty
@@ -846,6 +848,25 @@ int sfmx_matcher_stats(sfmx_matcher* m, int64_t* slow_queries, int64_t* fp32_pai
     if (fp32_pairs) *fp32_pairs = m->fp32_pairs;
     return SFMX_OK;
 }
+
+#ifdef SFMX_DIAG
+// Diagnostic build only (not part of the public interface): the last run's totals over the pairs of the
+// screen's two counters, forwarded queries and those of them on the full-row route of the FP6 product
+// path (0 on every other path, whose second counters stay zero).  Summed on the host.
+int sfmx_diag_matcher_route_totals(sfmx_matcher* m, int64_t* forwarded, int64_t* full_route) {
+    if (!m) return fail(SFMX_EINVAL, "null matcher");
+    if (!m->has_run) return fail(SFMX_ESTATE, "no totals before run");
+    DeviceGuard g(m->device);
+    std::vector<int32_t> h((size_t)arena_words(m->n_pairs));
+    HIPCHK(hipStreamSynchronize(m->run_stream));
+    HIPCHK(hipMemcpy(h.data(), m->qcount.p, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost));
+    int64_t a = 0, b = 0;
+    for (int p = 0; p < m->n_pairs; ++p) { a += h[p]; b += h[arena_qcount2(m->n_pairs) + p]; }
+    if (forwarded) *forwarded = a;
+    if (full_route) *full_route = b;
+    return SFMX_OK;
+}
+#endif
 
 int sfmx_matcher_timing(sfmx_matcher* m, float* main_kernel_ms, float* total_ms) {
     if (!m) return fail(SFMX_EINVAL, "null matcher");

@@ -1,7 +1,8 @@
 // SPDX-License-Identifier: MIT
 // Conservative FP6 (e2m3) first pass of the exact SIFT matcher: the quantiser, the packed row layout
 // and the bound arithmetic, for the device (match_kernels.hip) and for the host (tests/cpp/sift_fp6_main.cpp,
-// tests/test_sift_fp6_bound.py restates it in numpy).  No HIP header is needed to compile it for the host.
+// tests/test_sift_fp6_bound.py restates it in numpy; the one-subset certificate: tests/cpp/sift_fp6_cert_main.cpp,
+// tests/test_sift_fp6_cert.py).  No HIP header is needed to compile it for the host.
 //
 // Quantiser.  A descriptor value u (integer 0..255) is written  a = u - OFFSET = SCALE * m + e  with m the
 // nearest value an e2m3 element can hold, in units of 1/8:  +-{0..15, 16..30 step 2, 32..60 step 4}.  With
@@ -112,6 +113,35 @@ SFMX_FP6_HD int certainly_rejected(float k1, float k2, int na, int e2q, int emax
     lo = lo > 1.0e12 ? 1.0e12 : lo;
     const int64_t s1 = (int64_t)__builtin_floor(lo), s2 = (int64_t)__builtin_ceil(hi);
     return (int)!((double)sqrt_rn(s1) < (double)sqrt_rn(s2) * ratio);
+}
+
+// One-subset certificate.  k1 > k2 as above, r1 the row subset (j mod 16) of k1's row, nt the train rows.
+// With M = E + SLACK every row of subset r1's maximum has s <= s1hi and every row outside r1 has s >= lo,
+// some row outside it s <= hi:
+//     s1hi = ceil(max(na - 2 (1024 k1 - M), 0)),  lo = floor(max(na - 2 (1024 k2 + M), 0)),
+//     hi = ceil(max(na - 2 (1024 k2 - M), 0)).
+// 1: the query's best row lies in subset r1 strictly ahead of every row outside it (s1hi < lo: no index
+// tie across subsets), Lowe's test passes against every row outside it (at (s1hi, lo), monotone), the
+// exact s2 <= hi is below the float-sqrt collision range (SQRT_SAFE_S, the matcher's SQRT_SAFE), and the
+// subset holds two real rows (r1 + 16 < nt).  The exact top-2 (a1, a2) of subset r1 alone then settles the
+// query: s1 = a1, s2 = min(a2, s_other) with s_other in [lo, hi], and Lowe's test, which passes at every
+// s2 >= lo, fails at the true s2 exactly when it fails at a2 (sift_finish_kernel).
+constexpr int64_t SQRT_SAFE_S = 1 << 22;
+SFMX_FP6_HD int certified(float k1, float k2, int r1, int nt, int na, int e2q, int emax2, int amax2, double ratio) {
+    const double E = __builtin_sqrt((double)na * (double)emax2) +
+                     __builtin_sqrt((double)e2q) * (__builtin_sqrt((double)amax2) + __builtin_sqrt((double)emax2));
+    const double M = E + SLACK;
+    double s1 = (double)na - 2.0 * ((double)k1 * 1024.0 - M);
+    double lo = (double)na - 2.0 * ((double)k2 * 1024.0 + M);
+    double hi = (double)na - 2.0 * ((double)k2 * 1024.0 - M);
+    s1 = s1 < 0.0 ? 0.0 : (s1 > 1.0e12 ? 1.0e12 : s1);
+    lo = lo < 0.0 ? 0.0 : (lo > 1.0e12 ? 1.0e12 : lo);
+    hi = hi < 0.0 ? 0.0 : (hi > 1.0e12 ? 1.0e12 : hi);
+    // integers <= 10^12, exact in a double: compared and rooted as doubles (sqrt_rn of the same integers)
+    const double s1hi = __builtin_ceil(s1), slo = __builtin_floor(lo), shi = __builtin_ceil(hi);
+    const int usable = (int)(nt >= 2) & (int)(k2 > KEY_VALID);
+    const int lowe = (int)((double)(float)__builtin_sqrt(s1hi) < (double)(float)__builtin_sqrt(slo) * ratio);
+    return usable & (int)(s1hi < slo) & lowe & (int)(shi < (double)SQRT_SAFE_S) & (int)(r1 + 16 < nt);
 }
 
 }  // namespace fp6
