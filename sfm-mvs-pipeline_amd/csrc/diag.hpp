@@ -16,6 +16,9 @@ constexpr int SIFT_VARIANT_INT8_LISTS = 110;
 // SFMX_SIFT_VARIANT value (diagnostic build) of the list path with the FP6 screen and the full-row pass 2
 // for every forwarded query, the product path before the one-subset certificate: kept for the same uses.
 constexpr int SIFT_VARIANT_FP6_FULL = 111;
+// SFMX_SIFT_VARIANT value (diagnostic build) of the product path with the FP6 screen in the MFMA shape that
+// is not the product's (16 x 16 x 128 or 32 x 32 x 64, match_kernels.hip SIFT_SCREEN6_WIDE): kept for the same uses.
+constexpr int SIFT_VARIANT_FP6_OTHER_SHAPE = 112;
 
 #ifdef SFMX_DIAG
 #include <cstdlib>

@@ -852,6 +852,33 @@ void sift_screen16_kernel(const WorkItem* __restrict__ work, const PairDev* __re
     }
 }
 
+// The screen's decision for one query from its two largest subset maxima k1 >= k2 and k1's row subset r1
+// (both forms of the FP6 screen): rejected, or appended to the pair's list with its pass-2 route.
+template <bool CERT>
+__device__ __forceinline__ void screen6_forward(float k1, float k2, int r1, int qi, int nt, int2 q2, int emax2, int amax2,
+                                                double ratio, int pair, int64_t dense_base, int32_t* __restrict__ qlist,
+                                                int32_t* __restrict__ qcount, int32_t* __restrict__ qmask,
+                                                unsigned long long* __restrict__ top2, int32_t* __restrict__ qlist2,
+                                                int32_t* __restrict__ qcount2) {
+    // straight-line integer arithmetic decides (lowe_select: no bool PHI): the bound is usable with two
+    // train rows in two different subsets, every other query is forwarded
+    const int usable = (int)(nt >= 2) & (int)(k2 > fp6::KEY_VALID);
+    const int rej = usable & fp6::certainly_rejected(k1, k2, q2.x, q2.y, emax2, amax2, ratio);
+    if (rej == 0) {
+        const int64_t slot = dense_base + atomicAdd(&qcount[pair], 1);
+        qlist[slot] = qi;
+        if constexpr (CERT) {
+            const int cert = fp6::certified(k1, k2, r1, nt, q2.x, q2.y, emax2, amax2, ratio);
+            qmask[slot] = cert ? 1 << r1 : QMASK_FULL_ROUTE;
+            if (!cert) qlist2[dense_base + atomicAdd(&qcount2[pair], 1)] = (int32_t)(slot - dense_base);
+        } else {
+            qmask[slot] = 0xFFFF;   // not a two-bit mask: sift_finish_kernel reads the slot's own two keys
+        }
+        top2[2 * slot] = ~0ull;   // pass 2 overwrites both (a slot it misses counts as unsettled)
+        top2[2 * slot + 1] = ~0ull;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Screening pass of the product path on the FP6 matrix pipe: v_mfma_scale_f32_16x16x128_f8f6f4 with e2m3
 // operands, one MFMA (K = 128) per 16 x 16 tile, twice the MACs per clock of the int8 screens.  The
@@ -974,6 +1001,12 @@ void sift_screen6_kernel(const WorkItem* __restrict__ work, const PairDev* __res
     }
 
     const int emax2 = imax[2 * P.right], amax2 = imax[2 * P.right + 1];
+    // After the two shuffle rounds every lane group holds a tile's (k1, k2, r1), so lane group g decides tile
+    // 4 p + g: two passes of the decision (square roots in double, the certificate, the list atomics) with 64
+    // queries each instead of eight passes with 16 active lanes.
+    static_assert(QT % 4 == 0, "four tiles per decision pass");
+    float kk1[4] = {}, kk2[4] = {};
+    int rr1[4] = {};
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
         float k1 = fp6::KEY_INIT, k2 = fp6::KEY_INIT;
@@ -995,26 +1028,168 @@ void sift_screen6_kernel(const WorkItem* __restrict__ work, const PairDev* __res
             k2 = fmaxf(fminf(k1, p1), fmaxf(k2, p2));
             k1 = fmaxf(k1, p1);
         }
-        const int qi = qbase + qt * 16 + l16;
-        if (g != 0 || qi >= nq || nt == 0) continue;   // an empty train image: no neighbour, nothing to forward
-        // straight-line integer arithmetic decides (lowe_select: no bool PHI): the bound is usable with two
-        // train rows in two different subsets, every other query is forwarded
-        const int2 q2 = ne[L.row0 + qi];
-        const int usable = (int)(nt >= 2) & (int)(k2 > fp6::KEY_VALID);
-        const int rej = usable & fp6::certainly_rejected(k1, k2, q2.x, q2.y, emax2, amax2, ratio);
-        if (rej == 0) {
-            const int64_t slot = P.dense_base + atomicAdd(&qcount[w.pair], 1);
-            qlist[slot] = qi;
-            if constexpr (CERT) {
-                const int cert = fp6::certified(k1, k2, r1, nt, q2.x, q2.y, emax2, amax2, ratio);
-                qmask[slot] = cert ? 1 << r1 : QMASK_FULL_ROUTE;
-                if (!cert) qlist2[P.dense_base + atomicAdd(&qcount2[w.pair], 1)] = (int32_t)(slot - P.dense_base);
-            } else {
-                qmask[slot] = 0xFFFF;   // not a two-bit mask: sift_finish_kernel reads the slot's own two keys
-            }
-            top2[2 * slot] = ~0ull;   // pass 2 overwrites both (a slot it misses counts as unsettled)
-            top2[2 * slot + 1] = ~0ull;
+        kk1[qt & 3] = k1; kk2[qt & 3] = k2; rr1[qt & 3] = r1;
+        if ((qt & 3) != 3) continue;
+        k1 = kk1[0]; k2 = kk2[0]; r1 = rr1[0];
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+            k1 = g == j ? kk1[j] : k1;
+            k2 = g == j ? kk2[j] : k2;
+            r1 = g == j ? rr1[j] : r1;
         }
+        const int qi = qbase + ((qt & ~3) + g) * 16 + l16;
+        if (qi >= nq || nt == 0) continue;   // an empty train image: no neighbour, nothing to forward
+        screen6_forward<CERT>(k1, k2, r1, qi, nt, ne[L.row0 + qi], emax2, amax2, ratio, w.pair, P.dense_base, qlist, qcount,
+                              qmask, top2, qlist2, qcount2);
+    }
+}
+
+// The same screen on v_mfma_scale_f32_32x32x64_f8f6f4: two chained MFMAs (K = 64 each, the second takes the
+// first one's result as its C operand) per tile of 32 train rows x 32 queries, half the MFMA instructions
+// of the 16 x 16 form for the same products and the same 8 v_max3_f32 per tile.  Lane l owns query column
+// l & 31 and K-half h = l >> 5 (sift_fp6.hpp: fragments, accumulator rows, chains and LDS reads of this
+// form).  The 16 accumulator registers of a lane fold into 8 chains per query tile; the row subsets stay
+// "train row j mod 16", so everything behind the screen is the same.  A work item is 4 waves x 4 query
+// tiles of 32; the stage, its LDS-DMA fill and the rows in HBM are those of sift_screen6_kernel.
+// Fewer issue cycles but a lower held clock: 2.6 % slower on the step than the 16 x 16 form, which
+// stays the product; this one is SFMX_SIFT_VARIANT=112 of the diagnostic build.
+template <int WAVES, int MINW, int STAGE, bool CERT>
+__global__ __launch_bounds__(WAVES * 64, MINW)
+void sift_screen6w_kernel(const WorkItem* __restrict__ work, const PairDev* __restrict__ pairs,
+                          const ImgDev* __restrict__ imgs, const uint32_t* __restrict__ desc6,
+                          const float* __restrict__ keyf, const int2* __restrict__ ne,
+                          const int32_t* __restrict__ imax,
+                          int32_t* __restrict__ qlist, int32_t* __restrict__ qcount, double ratio,
+                          int32_t* __restrict__ qmask, unsigned long long* __restrict__ top2,
+                          int32_t* __restrict__ qlist2, int32_t* __restrict__ qcount2) {
+    constexpr int QT = 4;
+    static_assert(QT * WAVES * 32 == 512, "work items are 512 queries");
+    static_assert(WAVES == 4 && STAGE % 128 == 0 && ROW_ALIGN % STAGE == 0, "whole DMA instructions per wave; stages inside the padded rows");
+    constexpr int A_BYTES = STAGE * 64, B_BYTES = STAGE * 32;
+    constexpr int GA = A_BYTES / (WAVES * 64 * 16), GB = B_BYTES / (WAVES * 64 * 16), GK = STAGE / 64;
+    constexpr int BUF_BYTES = A_BYTES + B_BYTES + STAGE * 4;
+    __shared__ __attribute__((aligned(16))) char lds[2 * BUF_BYTES];
+
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5, l32 = lane & 31;
+    const WorkItem w = work[xcd_remap(blockIdx.x, gridDim.x)];
+    const PairDev P = pairs[w.pair];
+    const ImgDev L = imgs[P.left], R = imgs[P.right];
+    const int nq = L.rows, nt = R.rows;
+    const int qbase = w.q0 + wid * (QT * 32);
+
+    // Query fragments (B operand): fragment frag32(m, h) of the row for MFMA m
+    i32x8 bq[QT][2];
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+        const uint32_t* src = desc6 + (L.row0 + qbase + qt * 32 + l32) * fp6::ROW_WORDS;   // rows < rows_pad
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const int f = fp6::frag32(m, h);
+            const i32x4 lo = *reinterpret_cast<const i32x4*>(src + fp6::word_index(f, 0));
+            const int2 hi = *reinterpret_cast<const int2*>(src + fp6::word_index(f, 4));
+            bq[qt][m] = i32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, 0, 0};
+        }
+    }
+    float ch[QT][8];
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) ch[qt][c] = fp6::KEY_INIT;
+
+    const int nstages = (nt + STAGE - 1) / STAGE;
+    const char* tbase = reinterpret_cast<const char*>(desc6 + R.row0 * fp6::ROW_WORDS);
+    const float* kbase = keyf + R.row0;
+    auto stage = [&](int s, int buf) {   // as in sift_screen6_kernel
+        char* base = lds + buf * BUF_BYTES;
+#pragma unroll
+        for (int i = 0; i < GA; ++i) {   // plane A: 4 pieces per row
+            const int p = i * WAVES * 64 + threadIdx.x;
+            const int rr = p >> 2, c = (p & 3) ^ fp6::swz_a(rr);
+            const char* gp = tbase + (int64_t)(s * STAGE + rr) * fp6::ROW_BYTES + 16 * c;
+            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gp,
+                                             (LDS_AS void*)(base + (i * WAVES + wid) * 1024), 16, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < GB; ++i) {   // plane B: 2 pieces per row
+            const int p = i * WAVES * 64 + threadIdx.x;
+            const int rr = p >> 1, c = (p & 1) ^ fp6::swz_b(rr);
+            const char* gp = tbase + (int64_t)(s * STAGE + rr) * fp6::ROW_BYTES + 64 + 16 * c;
+            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gp,
+                                             (LDS_AS void*)(base + A_BYTES + (i * WAVES + wid) * 1024), 16, 0, 0);
+        }
+        if (wid < GK)
+            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(kbase + s * STAGE + wid * 64 + lane),
+                                             (LDS_AS void*)(base + A_BYTES + B_BYTES + wid * 256), 4, 0, 0);
+    };
+
+    if (nstages > 0) stage(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int s = 0; s < nstages; ++s) {
+        const int buf = s & 1;
+        if (s + 1 < nstages) stage(s + 1, buf ^ 1);
+        const char* base = lds + buf * BUF_BYTES;
+#pragma unroll
+        for (int t = 0; t < STAGE / 32; ++t) {
+            i32x8 a[2];
+            f32x16 key;
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const int f = fp6::frag32(m, h), row = t * 32 + l32;
+                const i32x4 lo = *reinterpret_cast<const i32x4*>(base + fp6::lds_a32(row, f));
+                const int2 hi = *reinterpret_cast<const int2*>(base + fp6::lds_b32(STAGE, row, f));
+                a[m] = i32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, 0, 0};
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {   // registers 4 k .. 4 k + 3: rows 8 k + 4 h .. + 3 of the block (fp6::acc_row32)
+                const f32x4 kv = *reinterpret_cast<const f32x4*>(base + fp6::lds_key32(STAGE, t * 32, k, h));
+                key[4 * k + 0] = kv.x; key[4 * k + 1] = kv.y; key[4 * k + 2] = kv.z; key[4 * k + 3] = kv.w;
+            }
+#pragma unroll
+            for (int qt = 0; qt < QT; ++qt) {
+                // format code 2 = e2m3 for both operands, unit E8M0 scales
+                f32x16 acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[0], bq[qt][0], key, 2, 2, 0, 0x7f7f7f7f, 0,
+                                                                             0x7f7f7f7f);
+                acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[1], bq[qt][1], acc, 2, 2, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+#pragma unroll
+                for (int c = 0; c < 8; ++c) ch[qt][c] = fmaxf(fmaxf(ch[qt][c], acc[c]), acc[c + 8]);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+
+    const int emax2 = imax[2 * P.right], amax2 = imax[2 * P.right + 1];
+    float kk1[2] = {}, kk2[2] = {};
+    int rr1[2] = {};
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+        float k1 = fp6::KEY_INIT, k2 = fp6::KEY_INIT;
+        int r1 = fp6::chain_subset32(0, h);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const float v = ch[qt][c];
+            if constexpr (CERT) r1 = v > k1 ? fp6::chain_subset32(c, h) : r1;
+            k2 = fmaxf(k2, fminf(k1, v));
+            k1 = fmaxf(k1, v);
+        }
+        {   // the other K-half's 8 subsets (equal maxima: either subset; k1 == k2 is never certified)
+            const float p1 = __shfl_xor(k1, 32), p2 = __shfl_xor(k2, 32);
+            if constexpr (CERT) {
+                const int pr = __shfl_xor(r1, 32);
+                r1 = p1 > k1 ? pr : r1;
+            }
+            k2 = fmaxf(fminf(k1, p1), fmaxf(k2, p2));
+            k1 = fmaxf(k1, p1);
+        }
+        // after the shuffle both halves hold the tile's (k1, k2, r1): half h decides tile 2 p + h, 64 queries a pass
+        kk1[qt & 1] = k1; kk2[qt & 1] = k2; rr1[qt & 1] = r1;
+        if ((qt & 1) != 1) continue;
+        k1 = h ? k1 : kk1[0]; k2 = h ? k2 : kk2[0]; r1 = h ? r1 : rr1[0];
+        const int qi = qbase + ((qt & ~1) + h) * 32 + l32;
+        if (qi >= nq || nt == 0) continue;   // an empty train image: no neighbour, nothing to forward
+        screen6_forward<CERT>(k1, k2, r1, qi, nt, ne[L.row0 + qi], emax2, amax2, ratio, w.pair, P.dense_base, qlist, qcount,
+                              qmask, top2, qlist2, qcount2);
     }
 }
 
@@ -2549,6 +2724,9 @@ int pass2_variant() {   // 10 = subset pass 2 (default), else the full-row GATHE
 // FP6 product path: the most full-route queries of a pair that ride the subset kernel (16 visits and the
 // atomic merge each) in place of one nearly empty 128-query full-row item (measured).
 constexpr int SIFT_RIDE_MAX = 32;
+// FP6 product path: the screen on 32 x 32 x 64 MFMAs (sift_screen6w_kernel) or on 16 x 16 x 128 ones
+// (sift_screen6_kernel); SIFT_VARIANT_FP6_OTHER_SHAPE runs the one that is not the product (measured).
+constexpr bool SIFT_SCREEN6_WIDE = false;
 int sift_block_queries(int v) { return v == 2 || v == 4 || v == 23 ? 256 : 512; }
 
 #define SIFT_LAUNCH(QT, W, MINW, ST, MF, ...)                                                             \
@@ -2586,17 +2764,23 @@ hipError_t launch_sift_knn2(const WorkItem* work, int n_work, const PairDev* pai
     if (v == 0 || v >= 101) {   // two-pass ratio test: screen every query, exact kernel on the rest
         hipError_t e = hipSuccess;   // qcount and the screen's XCD tickets behind it: zeroed by the caller's one fill
         if (lists) {   // product path: pass-2 state at the list slots; the caller settles with launch_finish_lists
-            if ((v != 0 && v != SIFT_VARIANT_INT8_LISTS && v != SIFT_VARIANT_FP6_FULL) || pass2_variant() != 10 || !qmask || !top2)
+            if ((v != 0 && v != SIFT_VARIANT_INT8_LISTS && v != SIFT_VARIANT_FP6_FULL && v != SIFT_VARIANT_FP6_OTHER_SHAPE) ||
+                pass2_variant() != 10 || !qmask || !top2)
                 return hipErrorInvalidValue;
-            if (v == 0) {
+            if (v == 0 || v == SIFT_VARIANT_FP6_OTHER_SHAPE) {
                 // conservative FP6 screen; exact pass 2 over the one certified row subset (one workgroup per
                 // pair and subset), and over every train row for the queries of the second list (128-query
                 // items).  The second list sits in `slot1`, idle here: no mask of this path has two bits.
                 if (!desc6 || !keyf || !ne || !imax || !slot1) return hipErrorInvalidValue;
                 int32_t* qlist2 = reinterpret_cast<int32_t*>(slot1);
                 int32_t* qcount2 = qcount + arena_qcount2(n_pairs);
-                sift_screen6_kernel<8, 4, 2, 128, true><<<n_work, 256, 0, st>>>(work, pairs, imgs, desc6, keyf, ne, imax, qlist,
-                                                                               qcount, ratio, qmask, top2, qlist2, qcount2);
+                // the screen's MFMA shape: the product's, or (diagnostic build) the other one
+                if (SIFT_SCREEN6_WIDE != (v == SIFT_VARIANT_FP6_OTHER_SHAPE))
+                    sift_screen6w_kernel<4, 2, 128, true><<<n_work, 256, 0, st>>>(work, pairs, imgs, desc6, keyf, ne, imax, qlist,
+                                                                                 qcount, ratio, qmask, top2, qlist2, qcount2);
+                else
+                    sift_screen6_kernel<8, 4, 2, 128, true><<<n_work, 256, 0, st>>>(work, pairs, imgs, desc6, keyf, ne, imax, qlist,
+                                                                                   qcount, ratio, qmask, top2, qlist2, qcount2);
                 if (ev_screen) {
                     e = hipEventRecord(ev_screen, st);
                     if (e != hipSuccess) return e;

@@ -417,10 +417,12 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
     const int nb_want = match_batches();
     // List path: the product SIFT path (FP6 screen, exact pass 2 over the certified subset or every row, one
     // batch) and its predecessors (SIFT_VARIANT_FP6_FULL: every row for every forwarded query;
-    // SIFT_VARIANT_INT8_LISTS: int8 screen, subset pass 2).  Every other diagnostic variant and
+    // SIFT_VARIANT_INT8_LISTS: int8 screen, subset pass 2; SIFT_VARIANT_FP6_OTHER_SHAPE: the product path with the
+    // screen's other MFMA shape).  Every other diagnostic variant and
     // ORB keep the dense per-query arrays; fp32-fallback pairs of a list run do too, per pair.
     const bool lists = m->norm == SFMX_NORM_L2 &&
-                       (variant_key == 0 || variant_key == SIFT_VARIANT_INT8_LISTS || variant_key == SIFT_VARIANT_FP6_FULL) &&
+                       (variant_key == 0 || variant_key == SIFT_VARIANT_INT8_LISTS || variant_key == SIFT_VARIANT_FP6_FULL ||
+                        variant_key == SIFT_VARIANT_FP6_OTHER_SHAPE) &&
                        pass2_variant() == 10 && nb_want == 1 &&
                        !persist_screens();
     const bool reuse = m->plan_valid && m->plan_variant == variant_key && m->plan_imgs == img_key && m->plan_nb == nb_want &&
@@ -865,6 +867,27 @@ int sfmx_diag_matcher_route_totals(sfmx_matcher* m, int64_t* forwarded, int64_t*
     if (forwarded) *forwarded = a;
     if (full_route) *full_route = b;
     return SFMX_OK;
+}
+// Diagnostic build only: what the batched prep wrote for the padded rows of image `img` of an L2 matcher:
+// desc6[rows_pad][24], keyf[rows_pad], ne[rows_pad][2], norm[rows_pad] and the image's imax[2]; any pointer
+// may be null.  -> rows_pad, or a (negative) SFMX_E* code.
+int sfmx_diag_matcher_prep_rows(sfmx_matcher* m, int img, uint32_t* desc6, float* keyf, int32_t* ne, int32_t* norm,
+                                int32_t* imax) {
+    if (!m) return fail(SFMX_EINVAL, "null matcher");
+    if (m->norm != SFMX_NORM_L2 || img < 0 || img >= m->n_imgs) return fail(SFMX_EINVAL, "no such L2 image");
+    DeviceGuard g(m->device);
+    if (hipDeviceSynchronize() != hipSuccess) return fail(SFMX_EINTERNAL, "device synchronize failed");
+    const ImgDev& d = m->imgs[img];
+    const size_t n = (size_t)d.rows_pad;
+    hipError_t e = hipSuccess;
+    if (desc6 && e == hipSuccess)
+        e = hipMemcpy(desc6, m->desc6.as<uint32_t>() + d.row0 * fp6::ROW_WORDS, n * fp6::ROW_BYTES, hipMemcpyDeviceToHost);
+    if (keyf && e == hipSuccess) e = hipMemcpy(keyf, m->keyf.as<float>() + d.row0, n * 4, hipMemcpyDeviceToHost);
+    if (ne && e == hipSuccess) e = hipMemcpy(ne, m->ne.as<int2>() + d.row0, n * sizeof(int2), hipMemcpyDeviceToHost);
+    if (norm && e == hipSuccess) e = hipMemcpy(norm, m->normv.as<int32_t>() + d.row0, n * 4, hipMemcpyDeviceToHost);
+    if (imax && e == hipSuccess) e = hipMemcpy(imax, m->imax.as<int32_t>() + 2 * img, 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(SFMX_EINTERNAL, hipGetErrorString(e));
+    return d.rows_pad;
 }
 #endif
 

@@ -24,8 +24,9 @@
 // 128 products and C, in any order, is below 2^14 in magnitude.  If each of the <= 129 additions loses at
 // most one f32 ulp at that magnitude (2^-9: round-to-nearest loses half of the 2^-10 ulp, truncation all
 // of it, and another factor 2 is left for alignment that keeps fewer bits), acc is off by < 129 * 2^-9
-// < 0.26, i.e. kappa~ by < 258.  SLACK = 1025 is four times that, plus 1 for the rounding of this
-// header's own double arithmetic (values < 2^27, a handful of roundings of 2^-26 each).
+// < 0.26, i.e. kappa~ by < 258 (the 32 x 32 x 64 form below: <= 130 additions, < 260).  SLACK = 1025 is four
+// times that, plus 1 for the rounding of this header's own double arithmetic (values < 2^27, a handful of
+// roundings of 2^-26 each).
 //
 // Screen.  Let K1 >= K2 be the two largest of the 16 row-subset maxima of kappa~: the maxima of two
 // different rows, both with kappa >= K2 - E - SLACK, and no row has kappa > K1 + E + SLACK.  Hence
@@ -95,8 +96,34 @@ inline void pack_row(const unsigned* codes /*128*/, uint32_t* out /*24*/) {
 // the fragment order through word_index alone).
 //   plane A: 64 B per row, piece c = g at slot c ^ swz_a(row); plane B: 32 B per row, piece c = g >> 1
 //   at slot c ^ swz_b(row).  tests/test_sift_fp6_bound.py enumerates the banks of every read group.
-SFMX_FP6_HD int swz_a(int row) { return (0 - (row >> 2)) & 3; }
-SFMX_FP6_HD int swz_b(int row) { return (row >> 3) & 1; }
+SFMX_FP6_HD constexpr int swz_a(int row) { return (0 - (row >> 2)) & 3; }
+SFMX_FP6_HD constexpr int swz_b(int row) { return (row >> 3) & 1; }
+
+// The 32 x 32 x 64 form of the screen (sift_screen6w_kernel): v_mfma_scale_f32_32x32x64_f8f6f4, two chained
+// MFMAs per tile of 32 train rows x 32 queries.  Lane l owns column l & 31 and K-half h = l >> 5; MFMA
+// m = 0, 1 of a tile takes fragment frag32(m, h) of the train row (A) and of the query (B): any bijection
+// onto the row's four fragments is correct as long as both operands use the same one.
+//   Accumulator register i = 0..15 of a lane with half h is train row acc_row32(i, h) of the 32-row block.
+//   Registers i and i + 8 are rows 16 apart, the same row subset j mod 16, so a lane folds them into 8
+//   chains, chain c = max3(chain c, acc[c], acc[c + 8]), and chain c of half h is row subset
+//   chain_subset32(c, h); the two halves of a column hold all 16 between them.
+//   Accumulation: the chained form rounds the intermediate accumulator once more, 130 additions instead
+//   of 129: acc is off by < 130 * 2^-9 < 0.26, kappa~ by < 2 * 130 = 260 key units, against SLACK = 1025.
+SFMX_FP6_HD constexpr int frag32(int m, int h) { return 2 * m + h; }
+SFMX_FP6_HD constexpr int acc_row32(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+SFMX_FP6_HD constexpr int chain_subset32(int c, int h) { return (c & 3) + 4 * h + 8 * (c >> 2); }
+// Byte offsets of that form's LDS reads inside a stage of STAGE rows (plane A | plane B | keys, the layout
+// and the swizzles of the 16 x 16 form).  Lane (row, h) reads fragment f = frag32(m, h): 16 B of plane A,
+// conflict-free in the ds_read_b128 lane groups, and 8 B of plane B.  The lanes of a 32-lane half all read
+// the same 8-B half of a 16-B piece, 32 banks for 64 words: a 2-way conflict under any swizzle of 16-B
+// pieces (two 8-B reads against six 16-B reads per row block).  The keys of registers 4 k .. 4 k + 3 are
+// four consecutive rows, one 16-B read per k, the same address in every lane of a half (broadcast).
+// tests/test_sift_fp6_screen32.py enumerates the banks.
+SFMX_FP6_HD constexpr int lds_a32(int row, int f) { return row * 64 + 16 * (f ^ swz_a(row)); }
+SFMX_FP6_HD constexpr int lds_b32(int stage, int row, int f) {
+    return stage * 64 + row * 32 + 16 * ((f >> 1) ^ swz_b(row)) + 8 * (f & 1);
+}
+SFMX_FP6_HD constexpr int lds_key32(int stage, int row0, int k, int h) { return stage * 96 + 4 * (row0 + 8 * k + 4 * h); }
 
 SFMX_FP6_HD float sqrt_rn(int64_t s) { return (float)__builtin_sqrt((double)s); }
 

@@ -1,0 +1,231 @@
+// Vector-issue cost of the block-scaled FP6 MFMA under the SIFT screen's fold density: register-resident
+// loops (no LDS, no global traffic inside the loop) on all 256 CUs, e2m3 operands quantised from SIFT-like
+// rows (fp6::quant_m / code_of_m of v ~ Exp(20): the held clock depends on operand bits).
+//   shape 16: v_mfma_scale_f32_16x16x128_f8f6f4, fresh C per MFMA, 0 / 1 / 2 v_max3_f32 per MFMA
+//   shape 32: v_mfma_scale_f32_32x32x64_f8f6f4 as two chained MFMAs, 0 / 4 / 8 v_max3_f32 per chained pair
+//             (the 8 are max3(ch[c], acc[c], acc[c + 8]))
+// each at 1 and at 3 waves per SIMD (dynamic LDS sets how many 256-thread workgroups share a CU).
+// One arm per process:  mfma_fp6_issue SHAPE FOLDS WAVES  -> one line: wall time per MFMA (per SIMD), the
+// held clock (d s_memtime / d s_memrealtime x 100 MHz, median over workgroups), cycles per MFMA and ops/s
+// as a fraction of the 10.07 PF FP6 peak.  Measurement only, never in the product.
+//   hipcc --offload-arch=gfx950 -O3 -o tools/micro/mfma_fp6_issue tools/micro/mfma_fp6_issue.hip
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <random>
+#include <vector>
+#include "../../sfm-mvs-pipeline_amd/csrc/sift_fp6.hpp"
+
+using namespace sfmx;
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int NROWS = 1 << 14;   // host-filled rows, a power of two
+constexpr int CUS = 256;
+
+// lane group g's 192-bit fragment of a packed row
+__device__ __forceinline__ i32x8 frag(const uint32_t* __restrict__ rows, int row, int g) {
+    const uint32_t* p = rows + (row & (NROWS - 1)) * fp6::ROW_WORDS;
+    return i32x8{(int)p[fp6::word_index(g, 0)], (int)p[fp6::word_index(g, 1)], (int)p[fp6::word_index(g, 2)],
+                 (int)p[fp6::word_index(g, 3)], (int)p[fp6::word_index(g, 4)], (int)p[fp6::word_index(g, 5)], 0, 0};
+}
+
+struct Stamp { long long cyc, real; };
+
+// 16 x 16 x 128: per iteration 8 query tiles x 2 row blocks = 16 MFMAs, FOLDS v_max3_f32 per MFMA
+template <int FOLDS>
+__global__ __launch_bounds__(256, 3) void arm16(const uint32_t* __restrict__ rows, int iters, float* __restrict__ out,
+                                                Stamp* __restrict__ st) {
+    extern __shared__ char occupancy_lds[];
+    const int lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
+    const int base = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 160;
+    i32x8 a[2], b[8];
+    for (int k = 0; k < 2; ++k) a[k] = frag(rows, base + 16 * k + l16, g);
+    for (int k = 0; k < 8; ++k) b[k] = frag(rows, base + 32 + 16 * k + l16, g);
+    f32x4 key[2], acc[8][2];
+    float ch[8][4];
+    for (int k = 0; k < 2; ++k) key[k] = f32x4{-(float)(lane + k), -2.f, -3.f, -4.f};
+    for (int q = 0; q < 8; ++q) {
+        for (int k = 0; k < 2; ++k) acc[q][k] = key[k];
+        for (int i = 0; i < 4; ++i) ch[q][i] = fp6::KEY_INIT;
+    }
+    const long long c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+    // Folds run one tile behind their MFMAs (two result sets in turn, the order pinned), so that a lone wave
+    // can issue them under the next tile's MFMAs.
+    auto pair = [&](int q, f32x4& x, f32x4& y) {
+        x = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[0], b[q], FOLDS == 0 ? acc[q][0] : key[0], 2, 2, 0, 0x7f7f7f7f,
+                                                             0, 0x7f7f7f7f);
+        y = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[1], b[q], FOLDS == 0 ? acc[q][1] : key[1], 2, 2, 0, 0x7f7f7f7f,
+                                                             0, 0x7f7f7f7f);
+    };
+    if constexpr (FOLDS == 0) {
+        for (int it = 0; it < iters; ++it) {
+            asm volatile("" : "+v"(a[0]), "+v"(a[1]));   // new rows each iteration as far as the compiler knows
+#pragma unroll
+            for (int q = 0; q < 8; ++q) pair(q, acc[q][0], acc[q][1]);
+        }
+    } else {
+        f32x4 x[2], y[2];
+        pair(0, x[0], y[0]);
+        for (int it = 0; it < iters; ++it) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                if (q == 7) asm volatile("" : "+v"(a[0]), "+v"(a[1]));
+                pair((q + 1) & 7, x[(q + 1) & 1], y[(q + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < 2 * FOLDS; ++i) ch[q][i] = fmaxf(fmaxf(ch[q][i], x[q & 1][i]), y[q & 1][i]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        acc[0][0] = x[0];   // the tile issued ahead of the last fold
+        acc[0][1] = y[0];
+    }
+    const long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    float s = 0.f;
+    for (int q = 0; q < 8; ++q)
+        for (int i = 0; i < 4; ++i) s += ch[q][i] * 1e-30f + acc[q][0][i] + acc[q][1][i];
+    out[blockIdx.x * 256 + threadIdx.x] = s;
+    if (threadIdx.x == 0) st[blockIdx.x] = Stamp{c1 - c0, r1 - r0};
+}
+
+// 32 x 32 x 64: per iteration 4 query tiles x 2 chained MFMAs = 8 MFMAs, FOLDS v_max3_f32 per chained pair
+template <int FOLDS>
+__global__ __launch_bounds__(256, 3) void arm32(const uint32_t* __restrict__ rows, int iters, float* __restrict__ out,
+                                                Stamp* __restrict__ st) {
+    extern __shared__ char occupancy_lds[];
+    const int lane = threadIdx.x & 63, h = lane >> 5, l32 = lane & 31;
+    const int base = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 160;
+    i32x8 a[2], b[4][2];
+    for (int m = 0; m < 2; ++m) a[m] = frag(rows, base + l32, 2 * m + h);
+    for (int q = 0; q < 4; ++q)
+        for (int m = 0; m < 2; ++m) b[q][m] = frag(rows, base + 32 + 32 * q + l32, 2 * m + h);
+    f32x16 key, acc[4];
+    float ch[4][8];
+    for (int i = 0; i < 16; ++i) key[i] = -(float)(lane + i);
+    for (int q = 0; q < 4; ++q) {
+        acc[q] = key;
+        for (int c = 0; c < 8; ++c) ch[q][c] = fp6::KEY_INIT;
+    }
+    const long long c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+    auto pair = [&](int q, f32x16& x) {
+        x = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[0], b[q][0], FOLDS == 0 ? acc[q] : key, 2, 2, 0, 0x7f7f7f7f, 0,
+                                                            0x7f7f7f7f);
+        x = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[1], b[q][1], x, 2, 2, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+    };
+    if constexpr (FOLDS == 0) {
+        for (int it = 0; it < iters; ++it) {
+            asm volatile("" : "+v"(a[0]), "+v"(a[1]));
+#pragma unroll
+            for (int q = 0; q < 4; ++q) pair(q, acc[q]);
+        }
+    } else {
+        f32x16 x[2];   // folds one tile behind, as in arm16
+        pair(0, x[0]);
+        for (int it = 0; it < iters; ++it) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (q == 3) asm volatile("" : "+v"(a[0]), "+v"(a[1]));
+                pair((q + 1) & 3, x[(q + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int c = 0; c < FOLDS; ++c) ch[q][c] = fmaxf(fmaxf(ch[q][c], x[q & 1][c]), x[q & 1][c + 8]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        acc[0] = x[0];
+    }
+    const long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    float s = 0.f;
+    for (int q = 0; q < 4; ++q) {
+        for (int c = 0; c < 8; ++c) s += ch[q][c] * 1e-30f;
+        for (int i = 0; i < 16; ++i) s += acc[q][i];
+    }
+    out[blockIdx.x * 256 + threadIdx.x] = s;
+    if (threadIdx.x == 0) st[blockIdx.x] = Stamp{c1 - c0, r1 - r0};
+}
+
+#define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 2; } } while (0)
+
+typedef void (*Arm)(const uint32_t*, int, float*, Stamp*);
+
+int main(int argc, char** argv) {
+    if (argc < 4) { fprintf(stderr, "usage: %s SHAPE(16|32) FOLDS WAVES(1|3) [seconds]\n", argv[0]); return 2; }
+    const int shape = atoi(argv[1]), folds = atoi(argv[2]), waves = atoi(argv[3]);
+    const double seconds = argc > 4 ? atof(argv[4]) : 2.0;
+    Arm k = nullptr;
+    if (shape == 16) k = folds == 0 ? arm16<0> : folds == 1 ? arm16<1> : folds == 2 ? arm16<2> : nullptr;
+    if (shape == 32) k = folds == 0 ? arm32<0> : folds == 4 ? arm32<4> : folds == 8 ? arm32<8> : nullptr;
+    if (!k || (waves != 1 && waves != 3)) { fprintf(stderr, "no such arm\n"); return 2; }
+    const int mfma_per_iter = shape == 16 ? 16 : 8;
+    const double ops_per_mfma = shape == 16 ? 16.0 * 16 * 128 * 2 : 32.0 * 32 * 64 * 2;
+    // 160 KB of LDS per CU: 96 KB lets one workgroup (one wave per SIMD) in, 48 KB three
+    const int lds = waves == 1 ? 96 * 1024 : 48 * 1024, blocks = CUS * waves;
+
+    std::vector<uint32_t> h((size_t)NROWS * fp6::ROW_WORDS);
+    std::mt19937 rng(7);
+    std::exponential_distribution<double> ex(1.0 / 20.0);
+    for (int r = 0; r < NROWS; ++r) {
+        unsigned codes[128];
+        for (int i = 0; i < 128; ++i)
+            codes[i] = fp6::code_of_m(fp6::quant_m((int)std::min(255.0, ex(rng)) - fp6::OFFSET));
+        fp6::pack_row(codes, h.data() + (size_t)r * fp6::ROW_WORDS);
+    }
+    uint32_t* d_rows;
+    float* d_out;
+    Stamp* d_st;
+    CHECK(hipMalloc(&d_rows, h.size() * 4));
+    CHECK(hipMalloc(&d_out, (size_t)blocks * 256 * 4));
+    CHECK(hipMalloc(&d_st, (size_t)blocks * sizeof(Stamp)));
+    CHECK(hipMemcpy(d_rows, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    int occ = 0;
+    CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k, 256, lds));
+    if (occ != waves) { fprintf(stderr, "occupancy %d workgroups per CU, wanted %d\n", occ, waves); return 3; }
+
+    // launches of ~20 ms, back to back for `seconds`; the last five are timed
+    int iters = 20000;
+    hipEvent_t e0, e1;
+    CHECK(hipEventCreate(&e0));
+    CHECK(hipEventCreate(&e1));
+    float ms = 0.f;
+    CHECK(hipEventRecord(e0));
+    k<<<blocks, 256, lds>>>(d_rows, iters, d_out, d_st);
+    CHECK(hipEventRecord(e1));
+    CHECK(hipEventSynchronize(e1));
+    CHECK(hipEventElapsedTime(&ms, e0, e1));
+    iters = std::max(1000, (int)(iters * 20.0 / std::max(ms, 0.01f)));
+    const auto t0 = std::chrono::steady_clock::now();
+    while (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < seconds) {
+        for (int i = 0; i < 4; ++i) k<<<blocks, 256, lds>>>(d_rows, iters, d_out, d_st);
+        CHECK(hipDeviceSynchronize());
+    }
+    std::vector<float> t(5);
+    std::vector<double> ghz;
+    for (int r = 0; r < 5; ++r) {
+        CHECK(hipEventRecord(e0));
+        k<<<blocks, 256, lds>>>(d_rows, iters, d_out, d_st);
+        CHECK(hipEventRecord(e1));
+        CHECK(hipEventSynchronize(e1));
+        CHECK(hipEventElapsedTime(&t[r], e0, e1));
+    }
+    std::vector<Stamp> st(blocks);
+    CHECK(hipMemcpy(st.data(), d_st, (size_t)blocks * sizeof(Stamp), hipMemcpyDeviceToHost));
+    for (const Stamp& s : st)
+        if (s.real > 0) ghz.push_back((double)s.cyc / (double)s.real * 0.1);
+    std::sort(ghz.begin(), ghz.end());
+    std::sort(t.begin(), t.end());
+    const double clock = ghz.empty() ? 0.0 : ghz[ghz.size() / 2], wall = t[2] * 1e-3;
+    // every SIMD runs `waves` waves of iters * mfma_per_iter MFMAs each
+    const double per_simd = (double)waves * iters * mfma_per_iter;
+    const double ns = wall / per_simd * 1e9, cyc = ns * clock;
+    const double frac = per_simd * CUS * 4 * ops_per_mfma / wall / 10.07e15;
+    printf("%dx%dx%d  %d v_max3 per %s  %d wave/SIMD  %7.3f ns/MFMA  clock %.3f GHz  %6.2f cyc/MFMA  %.3f of 10.07 PF  "
+           "(%.2f ms, min %.2f max %.2f)\n",
+           shape, shape, shape == 16 ? 128 : 64, folds, shape == 16 ? "MFMA" : "pair", waves, ns, clock, cyc, frac, t[2],
+           t[0], t[4]);
+    return 0;
+}
