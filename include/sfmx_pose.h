@@ -35,8 +35,8 @@
  *   - a pair the reference would throw cv::Exception for (fewer than 5
  *     matches, no model) has status 0, and its E and pose are the canonical
  *     quiet NaN.
- * solvePnPRansac (findCameraPoseFrom3d2dMatch, SfM.cpp:453-489) is not part of
- * this row.
+ * solvePnPRansac (findCameraPoseFrom3d2dMatch, SfM.cpp:453-489) is row f8:
+ * sfmx_register_poses in sfmx_pnp.h.
  *
  * Status codes and threading as in sfmx.h.  Calls on one device are serialised
  * inside the library; sfmx_relative_poses_last_kernel_ms is per calling thread.

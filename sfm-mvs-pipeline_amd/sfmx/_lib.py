@@ -95,7 +95,7 @@ class sfmx_cli_config(C.Structure):
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
 
-# Every symbol include/sfmx.h (and include/sfmx_ba.h, sfmx_homography.h, sfmx_triangulate.h, sfmx_pose.h, sfmx_scene.h) declares, with its ctypes prototype.
+# Every symbol include/sfmx.h (and include/sfmx_ba.h, sfmx_homography.h, sfmx_triangulate.h, sfmx_pose.h, sfmx_pnp.h, sfmx_scene.h) declares, with its ctypes prototype.
 _P = C.POINTER
 _i32p, _i64p, _vp = _P(C.c_int32), _P(C.c_int64), C.c_void_p
 PROTOTYPES = {
@@ -155,6 +155,13 @@ PROTOTYPES = {
                                       C.c_int32, _vp, _vp, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sfmx_relative_poses_last_kernel_ms": (C.c_float, []),
+    "sfmx_register_poses": (C.c_int, [_vp, _vp, _vp, _i32p, C.c_int32, _P(sfmx_tri_camera), C.c_int32, _i32p, _i32p,
+                                      C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sfmx_register_poses_last_kernel_ms": (C.c_float, []),
+    "sfmx_distinct_3d2d_points": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp,
+                                            _i64p]),
+    "sfmx_distinct_3d2d_last_kernel_ms": (C.c_float, []),
     "sfmx_find_3d2d_matches": (C.c_int, [_P(_vp), _i32p, C.c_int32, _i32p, C.c_int32, _vp, _vp, _vp, C.c_int32,
                                          _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "sfmx_find_3d2d_last_kernel_ms": (C.c_float, []),
