@@ -879,8 +879,54 @@ __device__ __forceinline__ void screen6_forward(float k1, float k2, int r1, int 
     }
 }
 
+// LDS stage of the FP6 screens (STAGE train rows: plane A | plane B | keys, the layout described at
+// sift_screen6_kernel) filled by 16-B LDS-DMA through two buffer resources, one over the train image's padded
+// packed rows and one over its keys.  Everything that changes from stage to stage is wave-uniform, so a lane's
+// byte offsets (swizzle included: a stage is a multiple of 16 rows, the period of fp6::swz_a / swz_b) are
+// computed once, and the stage advance goes into the instruction's scalar offset: no vector instruction per
+// stage.  The range check of the resources ends at the image's padded rows.
+template <int STAGE>
+struct Screen6Stage {
+    static constexpr int WAVES = 4;
+    static constexpr int A_BYTES = STAGE * 64, B_BYTES = STAGE * 32;
+    static constexpr int GA = A_BYTES / (WAVES * 64 * 16), GB = B_BYTES / (WAVES * 64 * 16), GK = STAGE / 64;
+    static constexpr int BUF_BYTES = A_BYTES + B_BYTES + STAGE * 4;
+    static_assert(STAGE % 128 == 0 && ROW_ALIGN % STAGE == 0, "whole DMA instructions per wave; stages inside the padded rows");
+    __amdgpu_buffer_rsrc_t rows, keys;
+    int va, vb, vk;   // per-lane byte offsets of the lane's plane-A piece, plane-B piece and key inside a stage
+    int wid;          // wave of the workgroup, in a scalar register
+
+    __device__ __forceinline__ Screen6Stage(const uint32_t* __restrict__ desc6, const float* __restrict__ keyf, const ImgDev& R) {
+        const int tid = threadIdx.x;
+        wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+        const int ra = tid >> 2, rb = tid >> 1;   // instruction i adds 64 (A) / 128 (B) rows: the swizzles do not change
+        va = ra * fp6::ROW_BYTES + 16 * ((tid & 3) ^ fp6::swz_a(ra));
+        vb = rb * fp6::ROW_BYTES + 64 + 16 * ((tid & 1) ^ fp6::swz_b(rb));
+        vk = (tid & 63) * 4;
+        rows = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(desc6 + R.row0 * fp6::ROW_WORDS), 0,
+                                                 R.rows_pad * fp6::ROW_BYTES, 0x00020000);
+        keys = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(keyf + R.row0), 0, R.rows_pad * 4, 0x00020000);
+    }
+    // stage s of the image into buffer `buf` of `lds` (2 x BUF_BYTES)
+    __device__ __forceinline__ void issue(char* lds, int s, int buf) const {
+        char* base = lds + buf * BUF_BYTES;
+        const int row0 = s * STAGE;
+#pragma unroll
+        for (int i = 0; i < GA; ++i)   // plane A: 4 pieces per row, 64 rows per instruction
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rows, (LDS_AS void*)(base + (i * WAVES + wid) * 1024), 16, va,
+                                                     (row0 + i * 64) * fp6::ROW_BYTES, 0, 0);
+#pragma unroll
+        for (int i = 0; i < GB; ++i)   // plane B: 2 pieces per row, 128 rows per instruction
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rows, (LDS_AS void*)(base + A_BYTES + (i * WAVES + wid) * 1024), 16, vb,
+                                                     (row0 + i * 128) * fp6::ROW_BYTES, 0, 0);
+        if (wid < GK)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(keys, (LDS_AS void*)(base + A_BYTES + B_BYTES + wid * 256), 4, vk,
+                                                     (row0 + wid * 64) * 4, 0, 0);
+    }
+};
+
 // ---------------------------------------------------------------------------
-// Screening pass of the product path on the FP6 matrix pipe: v_mfma_scale_f32_16x16x128_f8f6f4 with e2m3
+// Screening pass of the product path on the FP6 matrix pipe: v_mfma_f32_16x16x128_f8f6f4 (unscaled, fp6::mfma16) with e2m3
 // operands, one MFMA (K = 128) per 16 x 16 tile, twice the MACs per clock of the int8 screens.  The
 // operands are quantised, so the screen is conservative rather than exact (sift_fp6.hpp: quantiser, key,
 // bound and its proof): it rejects a query only when Lowe's test fails at a lower bound of s1 and an upper
@@ -910,17 +956,18 @@ void sift_screen6_kernel(const WorkItem* __restrict__ work, const PairDev* __res
                          int32_t* __restrict__ qmask, unsigned long long* __restrict__ top2,
                          int32_t* __restrict__ qlist2, int32_t* __restrict__ qcount2) {
     static_assert(QT * WAVES * 16 == 512, "work items are 512 queries");
-    static_assert(WAVES == 4 && STAGE % 128 == 0 && ROW_ALIGN % STAGE == 0, "whole DMA instructions per wave; stages inside the padded rows");
-    constexpr int A_BYTES = STAGE * 64, B_BYTES = STAGE * 32;
-    constexpr int GA = A_BYTES / (WAVES * 64 * 16), GB = B_BYTES / (WAVES * 64 * 16), GK = STAGE / 64;
-    constexpr int BUF_BYTES = A_BYTES + B_BYTES + STAGE * 4;
+    using Stage = Screen6Stage<STAGE>;
+    static_assert(WAVES == Stage::WAVES, "whole DMA instructions per wave");
+    constexpr int A_BYTES = Stage::A_BYTES, B_BYTES = Stage::B_BYTES, BUF_BYTES = Stage::BUF_BYTES;
     __shared__ __attribute__((aligned(16))) char lds[2 * BUF_BYTES];
 
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
+    const int lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
     const WorkItem w = work[xcd_remap(blockIdx.x, gridDim.x)];
     const PairDev P = pairs[w.pair];
     const ImgDev L = imgs[P.left], R = imgs[P.right];
     const int nq = L.rows, nt = R.rows;
+    const Stage stager(desc6, keyf, R);
+    const int wid = stager.wid;
     const int qbase = w.q0 + wid * (QT * 16);
 
     // Query fragments (B operand): lane group g's 192 bits of the row (fp6::word_index)
@@ -939,58 +986,41 @@ void sift_screen6_kernel(const WorkItem* __restrict__ work, const PairDev* __res
         for (int i = 0; i < 4; ++i) ch[qt][i] = fp6::KEY_INIT;
 
     const int nstages = (nt + STAGE - 1) / STAGE;
-    const char* tbase = reinterpret_cast<const char*>(desc6 + R.row0 * fp6::ROW_WORDS);
-    const float* kbase = keyf + R.row0;
-    auto stage = [&](int s, int buf) {
-        char* base = lds + buf * BUF_BYTES;
-#pragma unroll
-        for (int i = 0; i < GA; ++i) {   // plane A: 4 pieces per row
-            const int p = i * WAVES * 64 + threadIdx.x;
-            const int rr = p >> 2, c = (p & 3) ^ fp6::swz_a(rr);
-            const char* gp = tbase + (int64_t)(s * STAGE + rr) * fp6::ROW_BYTES + 16 * c;
-            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gp,
-                                             (LDS_AS void*)(base + (i * WAVES + wid) * 1024), 16, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < GB; ++i) {   // plane B: 2 pieces per row
-            const int p = i * WAVES * 64 + threadIdx.x;
-            const int rr = p >> 1, c = (p & 1) ^ fp6::swz_b(rr);
-            const char* gp = tbase + (int64_t)(s * STAGE + rr) * fp6::ROW_BYTES + 64 + 16 * c;
-            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gp,
-                                             (LDS_AS void*)(base + A_BYTES + (i * WAVES + wid) * 1024), 16, 0, 0);
-        }
-        if (wid < GK)
-            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(kbase + s * STAGE + wid * 64 + lane),
-                                             (LDS_AS void*)(base + A_BYTES + B_BYTES + wid * 256), 4, 0, 0);
-    };
+    // The lane's LDS reads: row block (t, b) is rows 16 (2 t + b) + l16, and the swizzles have a period of 16 rows,
+    // so a lane reads at three bases computed once (plane A, plane B, keys) plus a compile-time offset per
+    // buffer and row block, which goes into the ds_read offset field.
+    const char* ra = lds + l16 * 64 + 16 * (g ^ fp6::swz_a(l16));
+    const char* rb = lds + A_BYTES + l16 * 32 + 16 * ((g >> 1) ^ fp6::swz_b(l16)) + 8 * (g & 1);
+    const char* rk = lds + A_BYTES + B_BYTES + 16 * g;
+    static_assert(fp6::swz_a(16) == fp6::swz_a(0) && fp6::swz_b(16) == fp6::swz_b(0), "swizzle period of 16 rows");
 
-    if (nstages > 0) stage(0, 0);
+    if (nstages > 0) stager.issue(lds, 0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int s = 0; s < nstages; ++s) {
         const int buf = s & 1;
-        if (s + 1 < nstages) stage(s + 1, buf ^ 1);
-        const char* base = lds + buf * BUF_BYTES;
+        if (s + 1 < nstages) stager.issue(lds, s + 1, buf ^ 1);
+        // the buffer select is wave-uniform: one add per base and stage
+        const char *pa = ra + buf * BUF_BYTES, *pb = rb + buf * BUF_BYTES, *pk = rk + buf * BUF_BYTES;
 #pragma unroll
         for (int t = 0; t < STAGE / 32; ++t) {
             i32x8 a[2];
             f32x4 cinit[2];
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
-                const int row = t * 32 + b * 16 + l16;
-                const i32x4 lo = *reinterpret_cast<const i32x4*>(base + row * 64 + 16 * (g ^ fp6::swz_a(row)));
-                const int2 hi = *reinterpret_cast<const int2*>(base + A_BYTES + row * 32 +
-                                                               16 * ((g >> 1) ^ fp6::swz_b(row)) + 8 * (g & 1));
-                a[b] = i32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, 0, 0};
-                cinit[b] = *reinterpret_cast<const f32x4*>(base + A_BYTES + B_BYTES + 4 * (t * 32 + b * 16 + 4 * g));
+                const int blk = 2 * t + b;   // 16-row block of the stage
+                const i32x4 lo = *reinterpret_cast<const i32x4*>(pa + blk * 16 * 64);
+                // (volatile: one ds_read_b64 per fragment.  Merged into ds_read2st64_b64, the two row blocks' halves
+                // land in one register quad and cost four v_mov_b32 per 32 rows to reach their fragments.)
+                const long long hi = *(const volatile LDS_AS long long*)(pb + blk * 16 * 32);
+                a[b] = i32x8{lo.x, lo.y, lo.z, lo.w, (int)hi, (int)(hi >> 32), 0, 0};
+                cinit[b] = *reinterpret_cast<const f32x4*>(pk + blk * 16 * 4);
             }
 #pragma unroll
             for (int qt = 0; qt < QT; ++qt) {
-                // format code 2 = e2m3 for both operands, unit E8M0 scales
-                const f32x4 acc0 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[0], bq[qt], cinit[0], 2, 2, 0, 0x7f7f7f7f,
-                                                                                    0, 0x7f7f7f7f);
-                const f32x4 acc1 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[1], bq[qt], cinit[1], 2, 2, 0, 0x7f7f7f7f,
-                                                                                    0, 0x7f7f7f7f);
+                // e2m3 for both operands, the unit-scale product (fp6::mfma16)
+                const f32x4 acc0 = fp6::mfma16<fp6::FMT_E2M3, false>(a[0], bq[qt], cinit[0]);
+                const f32x4 acc1 = fp6::mfma16<fp6::FMT_E2M3, false>(a[1], bq[qt], cinit[1]);
                 // (folding one tile behind, the folds pinned under the next tile's MFMAs, measured slower: DESIGN 5)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) ch[qt][i] = fmaxf(fmaxf(ch[qt][i], acc0[i]), acc1[i]);
@@ -1044,7 +1074,7 @@ void sift_screen6_kernel(const WorkItem* __restrict__ work, const PairDev* __res
     }
 }
 
-// The same screen on v_mfma_scale_f32_32x32x64_f8f6f4: two chained MFMAs (K = 64 each, the second takes the
+// The same screen on v_mfma_f32_32x32x64_f8f6f4: two chained MFMAs (K = 64 each, the second takes the
 // first one's result as its C operand) per tile of 32 train rows x 32 queries, half the MFMA instructions
 // of the 16 x 16 form for the same products and the same 8 v_max3_f32 per tile.  Lane l owns query column
 // l & 31 and K-half h = l >> 5 (sift_fp6.hpp: fragments, accumulator rows, chains and LDS reads of this
@@ -1064,17 +1094,18 @@ void sift_screen6w_kernel(const WorkItem* __restrict__ work, const PairDev* __re
                           int32_t* __restrict__ qlist2, int32_t* __restrict__ qcount2) {
     constexpr int QT = 4;
     static_assert(QT * WAVES * 32 == 512, "work items are 512 queries");
-    static_assert(WAVES == 4 && STAGE % 128 == 0 && ROW_ALIGN % STAGE == 0, "whole DMA instructions per wave; stages inside the padded rows");
-    constexpr int A_BYTES = STAGE * 64, B_BYTES = STAGE * 32;
-    constexpr int GA = A_BYTES / (WAVES * 64 * 16), GB = B_BYTES / (WAVES * 64 * 16), GK = STAGE / 64;
-    constexpr int BUF_BYTES = A_BYTES + B_BYTES + STAGE * 4;
+    using Stage = Screen6Stage<STAGE>;   // the stage and its fill of sift_screen6_kernel
+    static_assert(WAVES == Stage::WAVES, "whole DMA instructions per wave");
+    constexpr int BUF_BYTES = Stage::BUF_BYTES;
     __shared__ __attribute__((aligned(16))) char lds[2 * BUF_BYTES];
 
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5, l32 = lane & 31;
+    const int lane = threadIdx.x & 63, h = lane >> 5, l32 = lane & 31;
     const WorkItem w = work[xcd_remap(blockIdx.x, gridDim.x)];
     const PairDev P = pairs[w.pair];
     const ImgDev L = imgs[P.left], R = imgs[P.right];
     const int nq = L.rows, nt = R.rows;
+    const Stage stager(desc6, keyf, R);
+    const int wid = stager.wid;
     const int qbase = w.q0 + wid * (QT * 32);
 
     // Query fragments (B operand): fragment frag32(m, h) of the row for MFMA m
@@ -1097,37 +1128,12 @@ void sift_screen6w_kernel(const WorkItem* __restrict__ work, const PairDev* __re
         for (int c = 0; c < 8; ++c) ch[qt][c] = fp6::KEY_INIT;
 
     const int nstages = (nt + STAGE - 1) / STAGE;
-    const char* tbase = reinterpret_cast<const char*>(desc6 + R.row0 * fp6::ROW_WORDS);
-    const float* kbase = keyf + R.row0;
-    auto stage = [&](int s, int buf) {   // as in sift_screen6_kernel
-        char* base = lds + buf * BUF_BYTES;
-#pragma unroll
-        for (int i = 0; i < GA; ++i) {   // plane A: 4 pieces per row
-            const int p = i * WAVES * 64 + threadIdx.x;
-            const int rr = p >> 2, c = (p & 3) ^ fp6::swz_a(rr);
-            const char* gp = tbase + (int64_t)(s * STAGE + rr) * fp6::ROW_BYTES + 16 * c;
-            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gp,
-                                             (LDS_AS void*)(base + (i * WAVES + wid) * 1024), 16, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < GB; ++i) {   // plane B: 2 pieces per row
-            const int p = i * WAVES * 64 + threadIdx.x;
-            const int rr = p >> 1, c = (p & 1) ^ fp6::swz_b(rr);
-            const char* gp = tbase + (int64_t)(s * STAGE + rr) * fp6::ROW_BYTES + 64 + 16 * c;
-            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gp,
-                                             (LDS_AS void*)(base + A_BYTES + (i * WAVES + wid) * 1024), 16, 0, 0);
-        }
-        if (wid < GK)
-            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(kbase + s * STAGE + wid * 64 + lane),
-                                             (LDS_AS void*)(base + A_BYTES + B_BYTES + wid * 256), 4, 0, 0);
-    };
-
-    if (nstages > 0) stage(0, 0);
+    if (nstages > 0) stager.issue(lds, 0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int s = 0; s < nstages; ++s) {
         const int buf = s & 1;
-        if (s + 1 < nstages) stage(s + 1, buf ^ 1);
+        if (s + 1 < nstages) stager.issue(lds, s + 1, buf ^ 1);
         const char* base = lds + buf * BUF_BYTES;
 #pragma unroll
         for (int t = 0; t < STAGE / 32; ++t) {
@@ -1147,10 +1153,9 @@ void sift_screen6w_kernel(const WorkItem* __restrict__ work, const PairDev* __re
             }
 #pragma unroll
             for (int qt = 0; qt < QT; ++qt) {
-                // format code 2 = e2m3 for both operands, unit E8M0 scales
-                f32x16 acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[0], bq[qt][0], key, 2, 2, 0, 0x7f7f7f7f, 0,
-                                                                             0x7f7f7f7f);
-                acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[1], bq[qt][1], acc, 2, 2, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+                // e2m3 for both operands, the unit-scale product (fp6::mfma32)
+                f32x16 acc = fp6::mfma32<fp6::FMT_E2M3, false>(a[0], bq[qt][0], key);
+                acc = fp6::mfma32<fp6::FMT_E2M3, false>(a[1], bq[qt][1], acc);
 #pragma unroll
                 for (int c = 0; c < 8; ++c) ch[qt][c] = fmaxf(fmaxf(ch[qt][c], acc[c]), acc[c + 8]);
             }
@@ -1472,6 +1477,44 @@ hipError_t launch_publish_flags(const int32_t* flags, int n, int32_t* dst, unsig
     return hipGetLastError();
 }
 #ifdef SFMX_DIAG
+// Diagnostic build only: both forms of the f8f6f4 MFMA (fp6::mfma16 / mfma32: block-scaled with unit scales,
+// and unscaled) on caller-supplied fragments, one wave per case (tests/test_gpu_mfma_unscaled.py).
+//   16 x 16 x 128: a, b [case][lane] fragments, c, d [case][lane] 4 floats
+//   32 x 32 x 64, the chained pair of the wide screen: a, b [case][m = 0, 1][lane], c, d [case][lane] 16 floats
+template <int FMT>
+__global__ __launch_bounds__(64)
+void mfma_forms16_kernel(const i32x8* __restrict__ a, const i32x8* __restrict__ b, const f32x4* __restrict__ c,
+                         f32x4* __restrict__ d_scaled, f32x4* __restrict__ d_unscaled) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    d_scaled[i] = fp6::mfma16<FMT, true>(a[i], b[i], c[i]);
+    d_unscaled[i] = fp6::mfma16<FMT, false>(a[i], b[i], c[i]);
+}
+template <int FMT>
+__global__ __launch_bounds__(64)
+void mfma_forms32_kernel(const i32x8* __restrict__ a, const i32x8* __restrict__ b, const f32x16* __restrict__ c,
+                         f32x16* __restrict__ d_scaled, f32x16* __restrict__ d_unscaled) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x, j = (int64_t)blockIdx.x * 128 + threadIdx.x;
+    d_scaled[i] = fp6::mfma32<FMT, true>(a[j + 64], b[j + 64], fp6::mfma32<FMT, true>(a[j], b[j], c[i]));
+    d_unscaled[i] = fp6::mfma32<FMT, false>(a[j + 64], b[j + 64], fp6::mfma32<FMT, false>(a[j], b[j], c[i]));
+}
+hipError_t launch_mfma_forms(int shape, int fmt, int n, const int32_t* a, const int32_t* b, const float* c, float* d_scaled,
+                             float* d_unscaled, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if ((shape != 16 && shape != 32) || (fmt != fp6::FMT_E2M3 && fmt != fp6::FMT_E2M1)) return hipErrorInvalidValue;
+    const i32x8 *pa = reinterpret_cast<const i32x8*>(a), *pb = reinterpret_cast<const i32x8*>(b);
+    if (shape == 16) {
+        const f32x4* pc = reinterpret_cast<const f32x4*>(c);
+        f32x4 *ds = reinterpret_cast<f32x4*>(d_scaled), *du = reinterpret_cast<f32x4*>(d_unscaled);
+        if (fmt == fp6::FMT_E2M3) mfma_forms16_kernel<fp6::FMT_E2M3><<<n, 64, 0, st>>>(pa, pb, pc, ds, du);
+        else mfma_forms16_kernel<fp6::FMT_E2M1><<<n, 64, 0, st>>>(pa, pb, pc, ds, du);
+    } else {
+        const f32x16* pc = reinterpret_cast<const f32x16*>(c);
+        f32x16 *ds = reinterpret_cast<f32x16*>(d_scaled), *du = reinterpret_cast<f32x16*>(d_unscaled);
+        if (fmt == fp6::FMT_E2M3) mfma_forms32_kernel<fp6::FMT_E2M3><<<n, 64, 0, st>>>(pa, pb, pc, ds, du);
+        else mfma_forms32_kernel<fp6::FMT_E2M1><<<n, 64, 0, st>>>(pa, pb, pc, ds, du);
+    }
+    return hipGetLastError();
+}
 hipError_t launch_probe_xor80(int8_t* p, int64_t bytes, hipStream_t st) {
     const int64_t n = bytes / 4;
     if (n == 0) return hipSuccess;
@@ -1625,8 +1668,8 @@ void sift_f32_kernel(const WorkItem* __restrict__ work, const int32_t* __restric
 // ORB Hamming 2-NN on the matrix cores (FP4 e2m1, +-1 encoding).
 //
 //   With bits mapped to +-1, dot(a, b) = 256 - 2 * hamming(a, b): an exact
-//   contraction of 256 products of +-1, i.e. 4 x v_mfma_scale_f32_32x32x64_f8f6f4
-//   (FP4 operands, unit E8M0 scales) per 32x32 tile — the same 128-byte rows
+//   contraction of 256 products of +-1, i.e. 4 x v_mfma_f32_32x32x64_f8f6f4
+//   (FP4 operands, unscaled: fp6::mfma32) per 32x32 tile — the same 128-byte rows
 //   and LDS stage as the SIFT kernel, at the FP4 rate (2x int8 per clock).
 //   The key needs no VALU: the MFMA's C operand is a per-train-row constant
 //       C_j = 767 + (16383 - (j & 16383)) / 16384
@@ -1731,12 +1774,10 @@ void orb_mfma_kernel(const WorkItem* __restrict__ work, const PairDev* __restric
             f32x16 acc[QT];
 #pragma unroll
             for (int qt = 0; qt < QT; ++qt) {
-                acc[qt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(i8of(a[0]), i8of(bq[qt][0]), cinit, 4, 4, 0,
-                                                                          0x7f7f7f7f, 0, 0x7f7f7f7f);
+                acc[qt] = fp6::mfma32<fp6::FMT_E2M1, false>(i8of(a[0]), i8of(bq[qt][0]), cinit);
 #pragma unroll
                 for (int m = 1; m < 4; ++m)
-                    acc[qt] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(i8of(a[m]), i8of(bq[qt][m]), acc[qt], 4, 4,
-                                                                              0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+                    acc[qt] = fp6::mfma32<fp6::FMT_E2M1, false>(i8of(a[m]), i8of(bq[qt][m]), acc[qt]);
             }
 #pragma unroll
             for (int qt = 0; qt < QT; ++qt) select(acc[qt], c1[qt], c2[qt]);
@@ -1779,7 +1820,7 @@ void orb_mfma_kernel(const WorkItem* __restrict__ work, const PairDev* __restric
     }
 }
 
-// ORB FP4 2-NN on v_mfma_scale_f32_16x16x128_f8f6f4: the same +-1 encoding,
+// ORB FP4 2-NN on v_mfma_f32_16x16x128_f8f6f4: the same +-1 encoding,
 // C-operand keys and chunked top-2 as orb_mfma_kernel, in the 16x16 shape (the
 // shape the SIFT screening pass holds a higher clock on).  K = 256 = 2 MFMAs per
 // 16x16 tile; lane l: A row / B column l & 15, operand chunk 4m + (l >> 4)
@@ -1886,10 +1927,8 @@ void orb_mfma16_kernel(const WorkItem* __restrict__ work, const PairDev* __restr
                 f32x4 acc[2];
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
-                    acc[b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(i8of(a[b][0]), i8of(bq[qt][0]), cinit[b], 4, 4,
-                                                                              0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-                    acc[b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(i8of(a[b][1]), i8of(bq[qt][1]), acc[b], 4, 4,
-                                                                              0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+                    acc[b] = fp6::mfma16<fp6::FMT_E2M1, false>(i8of(a[b][0]), i8of(bq[qt][0]), cinit[b]);
+                    acc[b] = fp6::mfma16<fp6::FMT_E2M1, false>(i8of(a[b][1]), i8of(bq[qt][1]), acc[b]);
                 }
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
@@ -2048,10 +2087,8 @@ void orb_screen16_kernel(const WorkItem* __restrict__ work, const PairDev* __res
                 f32x4 acc[2];
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
-                    acc[b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(i8of(a[b][0]), i8of(bq[qt][0]), cinit[b], 4, 4,
-                                                                              0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-                    acc[b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(i8of(a[b][1]), i8of(bq[qt][1]), acc[b], 4, 4,
-                                                                              0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+                    acc[b] = fp6::mfma16<fp6::FMT_E2M1, false>(i8of(a[b][0]), i8of(bq[qt][0]), cinit[b]);
+                    acc[b] = fp6::mfma16<fp6::FMT_E2M1, false>(i8of(a[b][1]), i8of(bq[qt][1]), acc[b]);
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) ch[qt][i] = fmaxf(fmaxf(ch[qt][i], acc[0][i]), acc[1][i]);
@@ -2118,7 +2155,7 @@ void orb_screen16_kernel(const WorkItem* __restrict__ work, const PairDev* __res
 }
 
 // ORB pass 2, subset form (default): as sift_subset_kernel, on the FP4 +-1 rows with
-// v_mfma_scale_f32_16x16x128_f8f6f4.  Subset r's rows j = r + 16 i get the C-operand key
+// v_mfma_f32_16x16x128_f8f6f4.  Subset r's rows j = r + 16 i get the C-operand key
 // 767 + (16383 - i) / 16384 (the local index keeps j's order), so a lane's float top-2 (v_med3_f32 /
 // v_max_f32) ranks (Hamming distance, j) exactly; one 16-query tile per wave pair of blocks.  The
 // (query, subset) top-2 is merged into the query's pair of 64-bit keys (d << 32) | j with atomicMin
@@ -2213,10 +2250,8 @@ void orb_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restri
                             f32x4 acc[2];
 #pragma unroll
                             for (int b = 0; b < 2; ++b) {
-                                acc[b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(i8of(a[b][0]), i8of(bq[qt][0]), cinit[b],
-                                                                                          4, 4, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-                                acc[b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(i8of(a[b][1]), i8of(bq[qt][1]), acc[b],
-                                                                                          4, 4, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+                                acc[b] = fp6::mfma16<fp6::FMT_E2M1, false>(i8of(a[b][0]), i8of(bq[qt][0]), cinit[b]);
+                                acc[b] = fp6::mfma16<fp6::FMT_E2M1, false>(i8of(a[b][1]), i8of(bq[qt][1]), acc[b]);
                             }
 #pragma unroll
                             for (int b = 0; b < 2; ++b)

@@ -32,6 +32,7 @@
 namespace sfmx {
 hipError_t launch_prep_l2(const float*, int, int, int, int8_t*, int32_t*, int32_t*, int32_t*, int32_t*, hipStream_t);
 hipError_t launch_probe_xor80(int8_t*, int64_t, hipStream_t);
+hipError_t launch_mfma_forms(int, int, int, const int32_t*, const int32_t*, const float*, float*, float*, hipStream_t);
 hipError_t launch_publish_flags(const int32_t*, int, int32_t*, unsigned*, unsigned, hipStream_t);
 hipError_t launch_prep_l2_batch(const PrepImg*, int, int, int8_t*, int32_t*, int32_t*, int32_t*, int32_t*, uint32_t*, float*,
                                 int2*, int32_t*, hipStream_t);
@@ -888,6 +889,54 @@ int sfmx_diag_matcher_prep_rows(sfmx_matcher* m, int img, uint32_t* desc6, float
     if (imax && e == hipSuccess) e = hipMemcpy(imax, m->imax.as<int32_t>() + 2 * img, 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(SFMX_EINTERNAL, hipGetErrorString(e));
     return d.rows_pad;
+}
+// Diagnostic build only: the int8 side of the same rows: desc8[rows_pad][128], keyc[rows_pad], keyc2[rows_pad]; any
+// pointer may be null.  -> rows_pad, or a (negative) SFMX_E* code.
+int sfmx_diag_matcher_prep_rows8(sfmx_matcher* m, int img, int8_t* desc8, int32_t* keyc, int32_t* keyc2) {
+    if (!m) return fail(SFMX_EINVAL, "null matcher");
+    if (m->norm != SFMX_NORM_L2 || img < 0 || img >= m->n_imgs) return fail(SFMX_EINVAL, "no such L2 image");
+    DeviceGuard g(m->device);
+    if (hipDeviceSynchronize() != hipSuccess) return fail(SFMX_EINTERNAL, "device synchronize failed");
+    const ImgDev& d = m->imgs[img];
+    const size_t n = (size_t)d.rows_pad;
+    hipError_t e = hipSuccess;
+    if (desc8 && e == hipSuccess)
+        e = hipMemcpy(desc8, m->desc8.as<int8_t>() + d.row0 * SIFT_DIM, n * SIFT_DIM, hipMemcpyDeviceToHost);
+    if (keyc && e == hipSuccess) e = hipMemcpy(keyc, m->keyc.as<int32_t>() + d.row0, n * 4, hipMemcpyDeviceToHost);
+    if (keyc2 && e == hipSuccess) e = hipMemcpy(keyc2, m->keyc2.as<int32_t>() + d.row0, n * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(SFMX_EINTERNAL, hipGetErrorString(e));
+    return d.rows_pad;
+}
+// Diagnostic build only: the f8f6f4 MFMA in both forms (fp6::mfma16 / mfma32, block-scaled with unit scales and
+// unscaled) on the caller's operand fragments and C values, one wave per case, D of each form back to the host.
+// shape 16: a, b [n][64][8] words, c, d [n][64][4] floats; shape 32 (the chained pair): a, b [n][2][64][8] words,
+// c, d [n][64][16] floats.  fmt: 2 = e2m3, 4 = e2m1.
+int sfmx_diag_mfma_forms(int device, int shape, int fmt, int n, const int32_t* a, const int32_t* b, const float* c,
+                         float* d_scaled, float* d_unscaled) {
+    if (n < 0 || (shape != 16 && shape != 32) || (fmt != 2 && fmt != 4) || !a || !b || !c || !d_scaled || !d_unscaled)
+        return fail(SFMX_EINVAL, "mfma forms: shape 16 | 32, fmt 2 | 4, no null array");
+    if (n == 0) return SFMX_OK;
+    DeviceGuard g(device);
+    const size_t ab = (size_t)n * (shape == 16 ? 1 : 2) * 64 * 8 * 4, cd = (size_t)n * 64 * (shape == 16 ? 4 : 16) * 4;
+    DevBuf da, db, dc, ds, du;
+    auto run = [&]() -> int {
+        for (DevBuf* buf : {&da, &db})
+            if (const int rc = buf->ensure(ab)) return rc;
+        for (DevBuf* buf : {&dc, &ds, &du})
+            if (const int rc = buf->ensure(cd)) return rc;
+        HIPCHK(hipMemcpy(da.p, a, ab, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(db.p, b, ab, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dc.p, c, cd, hipMemcpyHostToDevice));
+        HIPCHK(launch_mfma_forms(shape, fmt, n, da.as<int32_t>(), db.as<int32_t>(), dc.as<float>(), ds.as<float>(),
+                                 du.as<float>(), nullptr));
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(d_scaled, ds.p, cd, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(d_unscaled, du.p, cd, hipMemcpyDeviceToHost));
+        return SFMX_OK;
+    };
+    const int rc = run();
+    for (DevBuf* buf : {&da, &db, &dc, &ds, &du}) buf->release();
+    return rc;
 }
 #endif
 

@@ -11,7 +11,7 @@
 //
 // Keys.  For a query q and a train row t, with integer vectors a_q, a_t, the exact squared distance is
 //     s = |a_q|^2 - 2 kappa,   kappa = <a_q, a_t> - |a_t|^2 / 2
-// (the offset cancels in a_q - a_t).  The screen's MFMA computes, with unit block scales (an e2m3
+// (the offset cancels in a_q - a_t).  The screen's MFMA computes, unscaled, i.e. with unit block scales (an e2m3
 // element m stands for m / 8) and the f32 C operand keyf_t = -|a_t|^2 / 2048,
 //     acc = <m_q, m_t> / 64 + keyf_t,   kappa~ = 1024 acc = 16 <m_q, m_t> - |a_t|^2 / 2.
 //
@@ -99,7 +99,7 @@ inline void pack_row(const unsigned* codes /*128*/, uint32_t* out /*24*/) {
 SFMX_FP6_HD constexpr int swz_a(int row) { return (0 - (row >> 2)) & 3; }
 SFMX_FP6_HD constexpr int swz_b(int row) { return (row >> 3) & 1; }
 
-// The 32 x 32 x 64 form of the screen (sift_screen6w_kernel): v_mfma_scale_f32_32x32x64_f8f6f4, two chained
+// The 32 x 32 x 64 form of the screen (sift_screen6w_kernel): v_mfma_f32_32x32x64_f8f6f4, two chained
 // MFMAs per tile of 32 train rows x 32 queries.  Lane l owns column l & 31 and K-half h = l >> 5; MFMA
 // m = 0, 1 of a tile takes fragment frag32(m, h) of the train row (A) and of the query (B): any bijection
 // onto the row's four fragments is correct as long as both operands use the same one.
@@ -124,6 +124,29 @@ SFMX_FP6_HD constexpr int lds_b32(int stage, int row, int f) {
     return stage * 64 + row * 32 + 16 * ((f >> 1) ^ swz_b(row)) + 8 * (f & 1);
 }
 SFMX_FP6_HD constexpr int lds_key32(int stage, int row0, int k, int h) { return stage * 96 + 4 * (row0 + 8 * k + 4 * h); }
+
+#if defined(__HIPCC__)
+// The f8f6f4 MFMAs of the matcher (device only).  FMT is the element format code of both operands: 2 = e2m3
+// (the FP6 SIFT screens), 4 = e2m1 (the FP4 ORB kernels).  SCALED issues v_mfma_scale_f32_*_f8f6f4 with unit
+// E8M0 block scales (the 16-byte paired encoding: a scale load, then the MFMA, and one more VGPR read twice);
+// !SCALED passes constant zero scale arguments, for which the compiler selects the plain 8-byte
+// v_mfma_f32_*_f8f6f4: the unscaled instruction is the unit-scale product (tests/test_gpu_mfma_unscaled.py
+// compares the raw bits of D of both forms).
+constexpr int FMT_E2M3 = 2, FMT_E2M1 = 4;
+typedef int mfma_i32x8 __attribute__((ext_vector_type(8)));
+typedef float mfma_f32x4 __attribute__((ext_vector_type(4)));
+typedef float mfma_f32x16 __attribute__((ext_vector_type(16)));
+template <int FMT, bool SCALED>
+__device__ __forceinline__ mfma_f32x4 mfma16(mfma_i32x8 a, mfma_i32x8 b, mfma_f32x4 c) {
+    if constexpr (SCALED) return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, FMT, FMT, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+    else return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, FMT, FMT, 0, 0, 0, 0);
+}
+template <int FMT, bool SCALED>
+__device__ __forceinline__ mfma_f32x16 mfma32(mfma_i32x8 a, mfma_i32x8 b, mfma_f32x16 c) {
+    if constexpr (SCALED) return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, FMT, FMT, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+    else return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, FMT, FMT, 0, 0, 0, 0);
+}
+#endif
 
 SFMX_FP6_HD float sqrt_rn(int64_t s) { return (float)__builtin_sqrt((double)s); }
 

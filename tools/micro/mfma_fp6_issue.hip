@@ -1,11 +1,12 @@
-// Vector-issue cost of the block-scaled FP6 MFMA under the SIFT screen's fold density: register-resident
+// Vector-issue cost of the FP6 MFMA, block-scaled with unit scales and unscaled (fp6::mfma16 / mfma32: SHAPE 16 / 32
+// against 16u / 32u, printed as 16x16x128u / 32x32x64u), under the SIFT screen's fold density: register-resident
 // loops (no LDS, no global traffic inside the loop) on all 256 CUs, e2m3 operands quantised from SIFT-like
 // rows (fp6::quant_m / code_of_m of v ~ Exp(20): the held clock depends on operand bits).
 //   shape 16: v_mfma_scale_f32_16x16x128_f8f6f4, fresh C per MFMA, 0 / 1 / 2 v_max3_f32 per MFMA
 //   shape 32: v_mfma_scale_f32_32x32x64_f8f6f4 as two chained MFMAs, 0 / 4 / 8 v_max3_f32 per chained pair
 //             (the 8 are max3(ch[c], acc[c], acc[c + 8]))
 // each at 1 and at 3 waves per SIMD (dynamic LDS sets how many 256-thread workgroups share a CU).
-// One arm per process:  mfma_fp6_issue SHAPE FOLDS WAVES  -> one line: wall time per MFMA (per SIMD), the
+// One arm per process:  mfma_fp6_issue SHAPE[u] FOLDS WAVES  -> one line: wall time per MFMA (per SIMD), the
 // held clock (d s_memtime / d s_memrealtime x 100 MHz, median over workgroups), cycles per MFMA and ops/s
 // as a fraction of the 10.07 PF FP6 peak.  Measurement only, never in the product.
 //   hipcc --offload-arch=gfx950 -O3 -o tools/micro/mfma_fp6_issue tools/micro/mfma_fp6_issue.hip
@@ -14,6 +15,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 #include "../../sfm-mvs-pipeline_amd/csrc/sift_fp6.hpp"
@@ -36,7 +38,7 @@ __device__ __forceinline__ i32x8 frag(const uint32_t* __restrict__ rows, int row
 struct Stamp { long long cyc, real; };
 
 // 16 x 16 x 128: per iteration 8 query tiles x 2 row blocks = 16 MFMAs, FOLDS v_max3_f32 per MFMA
-template <int FOLDS>
+template <int FOLDS, bool SCALED>
 __global__ __launch_bounds__(256, 3) void arm16(const uint32_t* __restrict__ rows, int iters, float* __restrict__ out,
                                                 Stamp* __restrict__ st) {
     extern __shared__ char occupancy_lds[];
@@ -56,10 +58,8 @@ __global__ __launch_bounds__(256, 3) void arm16(const uint32_t* __restrict__ row
     // Folds run one tile behind their MFMAs (two result sets in turn, the order pinned), so that a lone wave
     // can issue them under the next tile's MFMAs.
     auto pair = [&](int q, f32x4& x, f32x4& y) {
-        x = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[0], b[q], FOLDS == 0 ? acc[q][0] : key[0], 2, 2, 0, 0x7f7f7f7f,
-                                                             0, 0x7f7f7f7f);
-        y = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a[1], b[q], FOLDS == 0 ? acc[q][1] : key[1], 2, 2, 0, 0x7f7f7f7f,
-                                                             0, 0x7f7f7f7f);
+        x = fp6::mfma16<fp6::FMT_E2M3, SCALED>(a[0], b[q], FOLDS == 0 ? acc[q][0] : key[0]);
+        y = fp6::mfma16<fp6::FMT_E2M3, SCALED>(a[1], b[q], FOLDS == 0 ? acc[q][1] : key[1]);
     };
     if constexpr (FOLDS == 0) {
         for (int it = 0; it < iters; ++it) {
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256, 3) void arm16(const uint32_t* __restrict__ row
 }
 
 // 32 x 32 x 64: per iteration 4 query tiles x 2 chained MFMAs = 8 MFMAs, FOLDS v_max3_f32 per chained pair
-template <int FOLDS>
+template <int FOLDS, bool SCALED>
 __global__ __launch_bounds__(256, 3) void arm32(const uint32_t* __restrict__ rows, int iters, float* __restrict__ out,
                                                 Stamp* __restrict__ st) {
     extern __shared__ char occupancy_lds[];
@@ -112,9 +112,8 @@ __global__ __launch_bounds__(256, 3) void arm32(const uint32_t* __restrict__ row
     }
     const long long c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
     auto pair = [&](int q, f32x16& x) {
-        x = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[0], b[q][0], FOLDS == 0 ? acc[q] : key, 2, 2, 0, 0x7f7f7f7f, 0,
-                                                            0x7f7f7f7f);
-        x = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[1], b[q][1], x, 2, 2, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+        x = fp6::mfma32<fp6::FMT_E2M3, SCALED>(a[0], b[q][0], FOLDS == 0 ? acc[q] : key);
+        x = fp6::mfma32<fp6::FMT_E2M3, SCALED>(a[1], b[q][1], x);
     };
     if constexpr (FOLDS == 0) {
         for (int it = 0; it < iters; ++it) {
@@ -153,12 +152,15 @@ __global__ __launch_bounds__(256, 3) void arm32(const uint32_t* __restrict__ row
 typedef void (*Arm)(const uint32_t*, int, float*, Stamp*);
 
 int main(int argc, char** argv) {
-    if (argc < 4) { fprintf(stderr, "usage: %s SHAPE(16|32) FOLDS WAVES(1|3) [seconds]\n", argv[0]); return 2; }
+    if (argc < 4) { fprintf(stderr, "usage: %s SHAPE(16|32|16u|32u) FOLDS WAVES(1|3) [seconds]\n", argv[0]); return 2; }
     const int shape = atoi(argv[1]), folds = atoi(argv[2]), waves = atoi(argv[3]);
+    const bool unscaled = strchr(argv[1], 'u') != nullptr;   // 16u / 32u: the plain v_mfma_f32_*_f8f6f4
     const double seconds = argc > 4 ? atof(argv[4]) : 2.0;
     Arm k = nullptr;
-    if (shape == 16) k = folds == 0 ? arm16<0> : folds == 1 ? arm16<1> : folds == 2 ? arm16<2> : nullptr;
-    if (shape == 32) k = folds == 0 ? arm32<0> : folds == 4 ? arm32<4> : folds == 8 ? arm32<8> : nullptr;
+    if (shape == 16 && !unscaled) k = folds == 0 ? arm16<0, true> : folds == 1 ? arm16<1, true> : folds == 2 ? arm16<2, true> : nullptr;
+    if (shape == 32 && !unscaled) k = folds == 0 ? arm32<0, true> : folds == 4 ? arm32<4, true> : folds == 8 ? arm32<8, true> : nullptr;
+    if (shape == 16 && unscaled) k = folds == 0 ? arm16<0, false> : folds == 1 ? arm16<1, false> : folds == 2 ? arm16<2, false> : nullptr;
+    if (shape == 32 && unscaled) k = folds == 0 ? arm32<0, false> : folds == 4 ? arm32<4, false> : folds == 8 ? arm32<8, false> : nullptr;
     if (!k || (waves != 1 && waves != 3)) { fprintf(stderr, "no such arm\n"); return 2; }
     const int mfma_per_iter = shape == 16 ? 16 : 8;
     const double ops_per_mfma = shape == 16 ? 16.0 * 16 * 128 * 2 : 32.0 * 32 * 64 * 2;
@@ -223,9 +225,9 @@ int main(int argc, char** argv) {
     const double per_simd = (double)waves * iters * mfma_per_iter;
     const double ns = wall / per_simd * 1e9, cyc = ns * clock;
     const double frac = per_simd * CUS * 4 * ops_per_mfma / wall / 10.07e15;
-    printf("%dx%dx%d  %d v_max3 per %s  %d wave/SIMD  %7.3f ns/MFMA  clock %.3f GHz  %6.2f cyc/MFMA  %.3f of 10.07 PF  "
+    printf("%dx%dx%d%s  %d v_max3 per %s  %d wave/SIMD  %7.3f ns/MFMA  clock %.3f GHz  %6.2f cyc/MFMA  %.3f of 10.07 PF  "
            "(%.2f ms, min %.2f max %.2f)\n",
-           shape, shape, shape == 16 ? 128 : 64, folds, shape == 16 ? "MFMA" : "pair", waves, ns, clock, cyc, frac, t[2],
+           shape, shape, shape == 16 ? 128 : 64, unscaled ? "u" : " ", folds, shape == 16 ? "MFMA" : "pair", waves, ns, clock, cyc, frac, t[2],
            t[0], t[4]);
     return 0;
 }
