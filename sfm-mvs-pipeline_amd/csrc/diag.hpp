@@ -19,6 +19,10 @@ constexpr int SIFT_VARIANT_FP6_FULL = 111;
 // SFMX_SIFT_VARIANT value (diagnostic build) of the product path with the FP6 screen in the MFMA shape that
 // is not the product's (16 x 16 x 128 or 32 x 32 x 64, match_kernels.hip SIFT_SCREEN6_WIDE): kept for the same uses.
 constexpr int SIFT_VARIANT_FP6_OTHER_SHAPE = 112;
+// SFMX_SIFT_VARIANT value (diagnostic build) of the product path with the certified route's pass 2 on
+// sift_subset_kernel (one workgroup per pair and subset, rows staged in LDS), the product path before
+// sift_rows_kernel: kept for the same uses.
+constexpr int SIFT_VARIANT_FP6_SUBSET_WG = 113;
 
 #ifdef SFMX_DIAG
 #include <cstdlib>

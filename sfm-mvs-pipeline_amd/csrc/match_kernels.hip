@@ -278,17 +278,20 @@ __global__ void prep_hamming_fp4_kernel(const uint8_t* __restrict__ src, int row
 // slot of `top2` as the two (s << 32) | j keys sift_finish_kernel merges for a mask of other than two bits.
 // VIA (with LISTS): the item's entries are those of the pair's second list (`qcount` = its counters): entry
 // e names the list slot `via[dense_base + e]`, whose query is gathered and whose two keys are written.
-template <int QT, int WAVES, int MINW, int STAGE, bool MFMA_FIRST, int PROBE = 0, int PIPE = 0, bool GATHER = false,
-          bool LISTS = false, bool VIA = false>
-__global__ __launch_bounds__(WAVES * 64, MINW)
-void sift_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restrict__ pairs,
-                      const ImgDev* __restrict__ imgs, const int8_t* __restrict__ desc8,
-                      const int32_t* __restrict__ norm, const int32_t* __restrict__ keyc,
-                      int32_t* __restrict__ out_idx, float* __restrict__ out_dist,
-                      int2* __restrict__ slow_list, int32_t* __restrict__ slow_count, double ratio,
-                      const int32_t* __restrict__ qlist = nullptr, const int32_t* __restrict__ qcount = nullptr,
-                      const int32_t* __restrict__ work2_n = nullptr, unsigned long long* __restrict__ top2 = nullptr,
-                      const int32_t* __restrict__ via = nullptr) {
+// The VIA launch is a fixed grid sized by the device, not by the job: workgroup b takes items b, b + gridDim.x,
+// ... < *work2_n (the XCD remap applies to the item index), each with the body of a one-item workgroup.
+//
+// One work item, `item` of `nwork` (workgroup-uniform).  Every wave leaves behind the barrier that follows the
+// last stage's reads (or, with no stage, the one before the loop), so the next item may restage the buffers.
+template <int QT, int WAVES, int MINW, int STAGE, bool MFMA_FIRST, int PROBE, int PIPE, bool GATHER, bool LISTS, bool VIA>
+__device__ __forceinline__
+void sift_knn2_item(const int item, const int nwork, const WorkItem* __restrict__ work, const PairDev* __restrict__ pairs,
+                    const ImgDev* __restrict__ imgs, const int8_t* __restrict__ desc8,
+                    const int32_t* __restrict__ norm, const int32_t* __restrict__ keyc,
+                    int32_t* __restrict__ out_idx, float* __restrict__ out_dist,
+                    int2* __restrict__ slow_list, int32_t* __restrict__ slow_count, double ratio,
+                    const int32_t* __restrict__ qlist, const int32_t* __restrict__ qcount,
+                    unsigned long long* __restrict__ top2, const int32_t* __restrict__ via) {
     static_assert(!LISTS || GATHER, "the list slots are the gathered entries");
     static_assert(!VIA || LISTS, "the second list names list slots");
     constexpr int GLDS = STAGE * SIFT_DIM / (WAVES * 64 * 16);   // 16-B LDS-DMA pieces per thread per stage
@@ -300,12 +303,7 @@ void sift_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restri
     __shared__ __attribute__((aligned(16))) char lds[2 * BUF_BYTES];
 
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5, l32 = lane & 31;
-    int nwork = gridDim.x;
-    if constexpr (GATHER) {           // compacted list of n2 work items; the grid is an upper bound
-        nwork = *work2_n;
-        if ((int)blockIdx.x >= nwork) return;
-    }
-    const WorkItem w = work[xcd_remap(blockIdx.x, nwork)];
+    const WorkItem w = work[xcd_remap(item, nwork)];
     const PairDev P = pairs[w.pair];
     const ImgDev L = imgs[P.left], R = imgs[P.right];
     const int nq = L.rows, nt = R.rows;
@@ -517,6 +515,33 @@ void sift_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restri
         out_idx[o] = lowe_select(J1[qt], d1, nt >= 2 ? sqrt_rn_int(s2) : 0.f, nt, ratio);
         out_dist[o] = d1;
     }
+}
+
+template <int QT, int WAVES, int MINW, int STAGE, bool MFMA_FIRST, int PROBE = 0, int PIPE = 0, bool GATHER = false,
+          bool LISTS = false, bool VIA = false>
+__global__ __launch_bounds__(WAVES * 64, MINW)
+void sift_knn2_kernel(const WorkItem* __restrict__ work, const PairDev* __restrict__ pairs,
+                      const ImgDev* __restrict__ imgs, const int8_t* __restrict__ desc8,
+                      const int32_t* __restrict__ norm, const int32_t* __restrict__ keyc,
+                      int32_t* __restrict__ out_idx, float* __restrict__ out_dist,
+                      int2* __restrict__ slow_list, int32_t* __restrict__ slow_count, double ratio,
+                      const int32_t* __restrict__ qlist = nullptr, const int32_t* __restrict__ qcount = nullptr,
+                      const int32_t* __restrict__ work2_n = nullptr, unsigned long long* __restrict__ top2 = nullptr,
+                      const int32_t* __restrict__ via = nullptr) {
+#define SIFT_KNN2_ITEM(item, nwork)                                                                                    \
+    sift_knn2_item<QT, WAVES, MINW, STAGE, MFMA_FIRST, PROBE, PIPE, GATHER, LISTS, VIA>(                               \
+        item, nwork, work, pairs, imgs, desc8, norm, keyc, out_idx, out_dist, slow_list, slow_count, ratio, qlist, qcount, \
+        top2, via)
+    if constexpr (VIA) {              // a fixed grid over the compacted list of *work2_n items
+        const int nwork = *work2_n;
+        for (int item = blockIdx.x; item < nwork; item += gridDim.x) SIFT_KNN2_ITEM(item, nwork);
+    } else if constexpr (GATHER) {    // compacted list of *work2_n work items; the grid is an upper bound
+        const int nwork = *work2_n;
+        if ((int)blockIdx.x < nwork) SIFT_KNN2_ITEM((int)blockIdx.x, nwork);
+    } else {
+        SIFT_KNN2_ITEM((int)blockIdx.x, (int)gridDim.x);
+    }
+#undef SIFT_KNN2_ITEM
 }
 
 // ---------------------------------------------------------------------------
@@ -1399,6 +1424,245 @@ void sift_subset_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restr
         __syncthreads();   // ql / s_n are rewritten by the next window
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // a staged chunk no group read: its LDS-DMA ends before the LDS is freed
+}
+
+// FP6 product path: the most full-route queries of a pair that ride the subset pass 2 (16 visits and the
+// atomic merge each) in place of one nearly empty 128-query full-row item (DESIGN 5: measured).
+constexpr int SIFT_RIDE_MAX = 32;
+
+// Pass 2, row form (the FP6 product path's certified route): one wave per (pair, row subset), one 256-thread
+// workgroup per (pair, group of four subsets); wave w of group G owns subset r = 4 G + w.  The FP6 screen's
+// masks have one bit (fp6::certified) or are QMASK_FULL_ROUTE, so a certified query belongs to exactly one
+// subset and the subset's unit is a wave: nothing but the gather is shared between the four waves.
+//
+// Gather, once per workgroup and 1024-entry window of the pair's forwarded list: every entry goes to at most
+// one of five lists in LDS, the four subsets' and the riders' (full-route entries of a pair with at most
+// SIFT_RIDE_MAX of them, which every wave takes behind its own list as if appended to all four), ranked by a
+// returning LDS atomic and placed after a barrier, so the lists share one pool of a window's size.  An entry
+// is query row | slot in the window << 20 | rider << 30.
+//
+// Rows: the wave streams its subset's rows j = r + 16 i in 32-row tiles through two 4-KB buffers of its own
+// (LDS-DMA, sift_subset_kernel's swizzle, the tile's norms beside it): the next tile lands under the one
+// being multiplied, tile 0 is issued at entry, under the gather, and the only wait is the wave's own counted
+// vmcnt: no workgroup barrier in the row loop.  (Loading the A operand straight from global memory, lane
+// (l32, h) the pieces 2 m + h of row l32, measured slower than sift_subset_kernel: each such instruction
+// touches 32 rows, 32 B of each, where eight lanes of a DMA fetch one whole row)
+// Every row r + 16 i, i < rows_pad / 16, lies in the image's padded rows (pad rows are zero; their keys are
+// INT_MIN, as those of the rows past nt).
+// Rows are the outer loop, the wave's up to QTMAX 32-query tiles the inner one (B fragments and the running
+// chunk top-2 in registers); more tiles take another pass over the rows.  The tile's 32 keys reach the
+// accumulator layout through a 128-B strip of LDS private to the wave (DS instructions of one wave execute
+// in order: no barrier).  Keys, 256-row chunks, the strict < of later chunks and the (s << 32) | j keys are
+// sift_subset_kernel's: both give the same top-2 of a (query, subset).
+//
+// Result: a certified slot has one writer, which stores (k1, k2) as one 16-B word over the slot's `top2`
+// pair (sift_finish_kernel clamps s2 for a one-bit mask); a rider takes sift_subset_kernel's three atomics.
+template <int QTMAX>
+__global__ __launch_bounds__(256, 4)
+void sift_rows_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restrict__ imgs,
+                      const int8_t* __restrict__ desc8, const int32_t* __restrict__ norm,
+                      const int32_t* __restrict__ qlist, const int32_t* __restrict__ qmask,
+                      const int32_t* __restrict__ qcount, const int32_t* __restrict__ qcount2,
+                      const int32_t* __restrict__ porder, unsigned long long* __restrict__ top2) {
+    constexpr int WIN = 1024;                 // forwarded-query window scanned per round
+    constexpr int EPT = WIN / 256;            // window entries per thread
+    constexpr int RIDER = 1 << 30;
+    constexpr int TILE = 32 * SIFT_DIM;       // bytes of a 32-row tile
+    __shared__ __attribute__((aligned(16))) char rows_lds[4][2][TILE];   // per wave: the tile being read, the one landing
+    __shared__ int nrm_lds[4][2][64];         // their norms (lanes 32..63 land a copy)
+    __shared__ int pool[WIN];                 // the five lists, back to back
+    __shared__ __attribute__((aligned(16))) int strip[4][32];
+    __shared__ int s_cnt[5];
+    // four workgroups per CU (160 KB of LDS), every wave working (128 VGPRs)
+    static_assert(sizeof(rows_lds) + sizeof(nrm_lds) + sizeof(pool) + sizeof(strip) + sizeof(s_cnt) <= 160 * 1024 / 4,
+                  "pass-2 LDS must leave four workgroups resident per CU");
+
+    const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, l32 = lane & 31;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the subset and all that follows from it
+    const int item = xcd_remap(blockIdx.x, gridDim.x);
+    const int pi = porder[item >> 2], G = item & 3, r = 4 * G + wid;
+    const int cnt = qcount[pi];
+    if (cnt == 0) return;
+    const PairDev P = pairs[pi];
+    const ImgDev L = imgs[P.left], R = imgs[P.right];
+    const int nt = R.rows;
+    if (4 * G >= nt) return;                  // no subset of the group has a row
+    const bool live = r < nt;                 // wave-uniform: an empty subset's wave only joins the barriers
+    const int ntile = R.rows_pad >> 9;        // 32-row tiles of a subset (rows_pad / 16 rows, a multiple of 32); >= 1
+    const int32_t* qls = qlist + P.dense_base;
+    const int32_t* qms = qmask + P.dense_base;
+    const bool riders = qcount2[pi] <= SIFT_RIDE_MAX;
+
+    const int8_t* rbase = desc8 + (R.row0 + r) * SIFT_DIM;   // scalar bases, one 32-bit lane offset each
+    const int32_t* nbase = norm + R.row0 + r;
+    // Tile t (< ntile: rows r + 16 i < rows_pad, i = 32 t + row) -> the wave's buffer b by LDS-DMA, five
+    // instructions: 16-B piece p = 64 u + lane of the tile is row p >> 3, slot p & 7, which holds the row's piece
+    // slot ^ ((row >> 1) & 7) (eight lanes fetch one whole 128-B row), and the norm of row l32.
+    auto stage = [&](int t, int b) {
+        const int8_t* src = rbase + (int64_t)t * (32 * 16 * SIFT_DIM);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int rr = 8 * u + (lane >> 3), c = (lane & 7) ^ ((rr >> 1) & 7);
+            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(src + (unsigned)(rr * (16 * SIFT_DIM) + 16 * c)),
+                                             (LDS_AS void*)(&rows_lds[wid][b][u * 1024]), 16, 0, 0);
+        }
+        __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(nbase + t * (32 * 16) + 16 * l32),
+                                         (LDS_AS void*)(&nrm_lds[wid][b][0]), 4, 0, 0);
+    };
+    int cur = 0;                              // the buffer of the next tile to read (tile 0 of the next pass)
+    if (live) stage(0, 0);
+
+    for (int e0 = 0; e0 < cnt; e0 += WIN) {
+        if (tid < 5) s_cnt[tid] = 0;
+        __syncthreads();
+        int ent[EPT], at[EPT], li[EPT];
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) {
+            const int e = e0 + k * 256 + tid;
+            li[k] = -1;
+            ent[k] = at[k] = 0;
+            if (e < cnt) {
+                const int mk = qms[e];
+                if (mk & QMASK_FULL_ROUTE) li[k] = riders ? 4 : -1;
+                else if (mk != 0 && ((__ffs(mk) - 1) >> 2) == G) li[k] = (__ffs(mk) - 1) & 3;
+                if (li[k] >= 0) {
+                    ent[k] = qls[e] | ((e - e0) << 20) | (li[k] == 4 ? RIDER : 0);
+                    at[k] = atomicAdd(&s_cnt[li[k]], 1);
+                }
+            }
+        }
+        __syncthreads();
+        int base[5], n_l[5];
+        base[0] = 0;
+#pragma unroll
+        for (int l = 0; l < 5; ++l) {
+            n_l[l] = __builtin_amdgcn_readfirstlane(s_cnt[l]);   // scalar, as everything sized by it
+            if (l < 4) base[l + 1] = base[l] + n_l[l];
+        }
+#pragma unroll
+        for (int k = 0; k < EPT; ++k)
+            if (li[k] >= 0) pool[base[li[k]] + at[k]] = ent[k];
+        __syncthreads();
+        const int n_own = n_l[wid], b_own = base[wid], n = live ? n_own + n_l[4] : 0;
+        for (int g0 = 0; g0 < n; g0 += 32 * QTMAX) {
+            const int nqt = min(QTMAX, (n - g0 + 31) >> 5);   // wave-uniform
+            // this lane's entry of tile qt (-1: none); read again in the epilogue, not kept across the row loop
+            auto entry = [&](int qt) {
+                const int qe = g0 + qt * 32 + l32;
+                return qe < n ? (qe < n_own ? pool[b_own + qe] : pool[base[4] + qe - n_own]) : -1;
+            };
+            i32x4 bq[QTMAX][4];
+#pragma unroll
+            for (int qt = 0; qt < QTMAX; ++qt) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m) bq[qt][m] = i32x4{0, 0, 0, 0};
+                if (qt < nqt) {
+                    const int qpk = entry(qt);
+                    const int64_t lrow = L.row0 + (qpk < 0 ? 0 : (qpk & 0xFFFFF));
+                    const i32x4* src = reinterpret_cast<const i32x4*>(desc8 + lrow * SIFT_DIM);
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) bq[qt][m] = src[2 * m + h];
+                }
+            }
+            int T1[QTMAX], T2[QTMAX], c1[QTMAX], c2[QTMAX];
+            unsigned JJ[QTMAX];   // J1 | J2 << 16: subset rows i < rows_pad / 16 <= 2^14 (an image has fewer than 2^18 rows)
+#pragma unroll
+            for (int qt = 0; qt < QTMAX; ++qt) {
+                T1[qt] = T2[qt] = INT_MAX; JJ[qt] = 0; c1[qt] = c2[qt] = INT_MIN;
+            }
+            for (int t = 0; t < ntile; ++t) {
+                stage(t + 1 < ntile ? t + 1 : 0, cur ^ 1);   // (tile 0 again: the next pass's or window's first)
+                // tile t has landed once at most the five instructions above are outstanding (vector memory
+                // instructions retire in order; whatever else was issued since only tightens the wait)
+                // The reads are written out: before a ds_read the compiler has seen, it waits for every LDS-DMA in
+                // flight (vmcnt(0)), the tile just issued included, which would undo the overlap.
+                int nv;
+                i32x4 a[4];
+                {
+                    const unsigned rb = (unsigned)(size_t)(LDS_AS const void*)&rows_lds[wid][cur][l32 * SIFT_DIM];
+                    const unsigned sw = (l32 >> 1) & 7;
+                    asm volatile("s_waitcnt vmcnt(5)\n\t"
+                                 "ds_read_b32 %0, %5\n\t"
+                                 "ds_read_b128 %1, %6\n\t"
+                                 "ds_read_b128 %2, %7\n\t"
+                                 "ds_read_b128 %3, %8\n\t"
+                                 "ds_read_b128 %4, %9\n\t"
+                                 "s_waitcnt lgkmcnt(0)"
+                                 : "=&v"(nv), "=&v"(a[0]), "=&v"(a[1]), "=&v"(a[2]), "=&v"(a[3])
+                                 : "v"((unsigned)(size_t)(LDS_AS const void*)&nrm_lds[wid][cur][l32]),
+                                   "v"(rb + 16 * ((0 + h) ^ sw)), "v"(rb + 16 * ((2 + h) ^ sw)),
+                                   "v"(rb + 16 * ((4 + h) ^ sw)), "v"(rb + 16 * ((6 + h) ^ sw))
+                                 : "memory");
+                }
+                cur ^= 1;
+                const int i = t * 32 + l32;
+                strip[wid][l32] = r + 16 * i < nt ? -(nv << 8) + 255 - (i & 255) : INT_MIN;   // (both halves: the same word)
+                asm volatile("" ::: "memory");   // the strip is the wave's own: its DS instructions execute in order
+                i32x4 kv[4];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) kv[g] = *reinterpret_cast<const i32x4*>(&strip[wid][8 * g + 4 * h]);
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int qt = 0; qt < QTMAX; ++qt) {
+                    if (qt >= nqt) continue;
+                    i32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[m], bq[qt][m], acc, 0, 0, 0);
+#pragma unroll
+                    for (int q = 0; q < 16; q += 4) {   // (c2 every four keys: two medians live, not eight)
+                        int mm[2];
+#pragma unroll
+                        for (int u = 0; u < 4; u += 2) {
+                            const int ka = (int)(((unsigned)acc[q + u] << 9) + (unsigned)kv[q >> 2][u]);
+                            const int kb = (int)(((unsigned)acc[q + u + 1] << 9) + (unsigned)kv[q >> 2][u + 1]);
+                            mm[u >> 1] = v_med3(c1[qt], ka, kb);
+                            c1[qt] = v_max3(c1[qt], ka, kb);
+                        }
+                        c2[qt] = v_max3(mm[0], mm[1], c2[qt]);
+                    }
+                }
+                if ((t & 7) == 7 || t + 1 == ntile) {   // end of a 256-row chunk
+                    const int cb = (t >> 3) * 256;
+#pragma unroll
+                    for (int qt = 0; qt < QTMAX; ++qt) {
+                        const int p1 = __shfl_xor(c1[qt], 32), p2 = __shfl_xor(c2[qt], 32);
+                        const int m1 = max(c1[qt], p1), m2 = max(min(c1[qt], p1), max(c2[qt], p2));
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) {   // chunk top-2 into the running top-2 (later chunks: strict <)
+                            const int key = e == 0 ? m1 : m2;
+                            if (key != INT_MIN) {
+                                const int t_ = -(key >> 8), i_ = cb + 255 - (key & 255);
+                                if (t_ < T2[qt]) {
+                                    if (t_ < T1[qt]) { T2[qt] = T1[qt]; T1[qt] = t_; JJ[qt] = (JJ[qt] << 16) | (unsigned)i_; }
+                                    else { T2[qt] = t_; JJ[qt] = (JJ[qt] & 0xFFFFu) | ((unsigned)i_ << 16); }
+                                }
+                            }
+                        }
+                        c1[qt] = c2[qt] = INT_MIN;
+                    }
+                }
+            }
+            // (T1, J1) <= (T2, J2) in (distance, index) order: k1 <= k2 (the merge at sift_subset_kernel)
+#pragma unroll
+            for (int qt = 0; qt < QTMAX; ++qt) {
+                const int qpk = qt < nqt ? entry(qt) : -1;
+                if (h != 0 || qpk < 0) continue;
+                const long long nq = norm[L.row0 + (qpk & 0xFFFFF)];
+                const unsigned long long k1 = T1[qt] != INT_MAX ? ((unsigned long long)(nq + T1[qt]) << 32) | (unsigned)(r + 16 * (JJ[qt] & 0xFFFFu)) : ~0ull;
+                const unsigned long long k2 = T2[qt] != INT_MAX ? ((unsigned long long)(nq + T2[qt]) << 32) | (unsigned)(r + 16 * (JJ[qt] >> 16)) : ~0ull;
+                unsigned long long* b = top2 + 2 * (P.dense_base + e0 + ((qpk >> 20) & (WIN - 1)));
+                if (!(qpk & RIDER)) {   // certified: this wave is the slot's only writer
+                    *reinterpret_cast<ulonglong2*>(b) = make_ulonglong2(k1, k2);
+                } else if (T1[qt] != INT_MAX) {
+                    if (T2[qt] != INT_MAX) atomicMin(b + 1, k2);
+                    const unsigned long long old = atomicMin(b, k1);
+                    atomicMin(b + 1, old > k1 ? old : k1);
+                }
+            }
+        }
+        __syncthreads();   // pool / s_cnt are rewritten by the next window
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tile still landing: its LDS-DMA ends before the LDS is freed
 }
 
 // Pass 2, subset form: the forwarded queries' merged top-2 -> dense results (one workgroup per pair).
@@ -2756,12 +3020,20 @@ int pass2_variant() {   // 10 = subset pass 2 (default), else the full-row GATHE
     const char* e = SFMX_DIAG_ENV("SFMX_SIFT_P2");   // with that item size (0 / 2 = 128 queries)
     return e ? atoi(e) : 10;
 }
-// FP6 product path: the most full-route queries of a pair that ride the subset kernel (16 visits and the
-// atomic merge each) in place of one nearly empty 128-query full-row item (DESIGN 5: measured).
-constexpr int SIFT_RIDE_MAX = 32;
 // FP6 product path: the screen on 32 x 32 x 64 MFMAs (sift_screen6w_kernel) or on 16 x 16 x 128 ones
 // (sift_screen6_kernel); SIFT_VARIANT_FP6_OTHER_SHAPE runs the one that is not the product (measured).
 constexpr bool SIFT_SCREEN6_WIDE = false;
+// FP6 product path: 32-query tiles a wave of sift_rows_kernel carries per pass over its subset's rows.  Two fit
+// the 128 VGPRs of four waves per SIMD without scratch (126); three spill 13 registers.
+constexpr int SIFT_ROWS_QT = 2;
+// FP6 product path: resident workgroups assumed for the full-row launch where the occupancy query fails
+// (256 CUs x 4), and (diagnostic build) SFMX_FULL_ROW_GRID, which sets that launch's grid (tests: several items
+// per workgroup on a small job).
+constexpr int SIFT_FULL_ROW_SLOTS = 1024;
+int full_row_grid(int dflt) {
+    const char* e = SFMX_DIAG_ENV("SFMX_FULL_ROW_GRID");
+    return e ? std::max(1, atoi(e)) : dflt;
+}
 int sift_block_queries(int v) { return v == 2 || v == 4 || v == 23 ? 256 : 512; }
 
 #define SIFT_LAUNCH(QT, W, MINW, ST, MF, ...)                                                             \
@@ -2799,12 +3071,14 @@ hipError_t launch_sift_knn2(const WorkItem* work, int n_work, const PairDev* pai
     if (v == 0 || v >= 101) {   // two-pass ratio test: screen every query, exact kernel on the rest
         hipError_t e = hipSuccess;   // qcount and the screen's XCD tickets behind it: zeroed by the caller's one fill
         if (lists) {   // product path: pass-2 state at the list slots; the caller settles with launch_finish_lists
-            if ((v != 0 && v != SIFT_VARIANT_INT8_LISTS && v != SIFT_VARIANT_FP6_FULL && v != SIFT_VARIANT_FP6_OTHER_SHAPE) ||
+            if ((v != 0 && v != SIFT_VARIANT_INT8_LISTS && v != SIFT_VARIANT_FP6_FULL && v != SIFT_VARIANT_FP6_OTHER_SHAPE &&
+                 v != SIFT_VARIANT_FP6_SUBSET_WG) ||
                 pass2_variant() != 10 || !qmask || !top2)
                 return hipErrorInvalidValue;
-            if (v == 0 || v == SIFT_VARIANT_FP6_OTHER_SHAPE) {
-                // conservative FP6 screen; exact pass 2 over the one certified row subset (one workgroup per
-                // pair and subset), and over every train row for the queries of the second list (128-query
+            if (v == 0 || v == SIFT_VARIANT_FP6_OTHER_SHAPE || v == SIFT_VARIANT_FP6_SUBSET_WG) {
+                // conservative FP6 screen; exact pass 2 over the one certified row subset (one wave per pair
+                // and subset: sift_rows_kernel; diagnostic build, SIFT_VARIANT_FP6_SUBSET_WG: one workgroup,
+                // sift_subset_kernel), and over every train row for the queries of the second list (128-query
                 // items).  The second list sits in `slot1`, idle here: no mask of this path has two bits.
                 if (!desc6 || !keyf || !ne || !imax || !slot1) return hipErrorInvalidValue;
                 int32_t* qlist2 = reinterpret_cast<int32_t*>(slot1);
@@ -2820,10 +3094,18 @@ hipError_t launch_sift_knn2(const WorkItem* work, int n_work, const PairDev* pai
                     e = hipEventRecord(ev_screen, st);
                     if (e != hipSuccess) return e;
                 }
-                sift_subset_kernel<4, true><<<n_pairs * 16, 256, 0, st>>>(pairs, imgs, desc8, norm, qlist, qmask, qcount, porder,
-                                                                          top2, slot1, qcount2, SIFT_RIDE_MAX);
+                if (v == SIFT_VARIANT_FP6_SUBSET_WG)
+                    sift_subset_kernel<4, true><<<n_pairs * 16, 256, 0, st>>>(pairs, imgs, desc8, norm, qlist, qmask, qcount, porder,
+                                                                              top2, slot1, qcount2, SIFT_RIDE_MAX);
+                else
+                    sift_rows_kernel<SIFT_ROWS_QT><<<n_pairs * 4, 256, 0, st>>>(pairs, imgs, desc8, norm, qlist, qmask, qcount,
+                                                                                 qcount2, porder, top2);
                 compact_work_kernel<7><<<1, 1024, 0, st>>>(porder, n_pairs, qcount2, work2, work2_n, SIFT_RIDE_MAX);
-                sift_knn2_kernel<1, 4, 2, 128, false, 0, 0, true, true, true><<<n_work << 2, 256, 0, st>>>(   // work2 holds n_work << 2 items
+                // the full-row items (work2 holds up to n_work << 2 of them; the count stays on the device): a
+                // grid of two resident rounds, each workgroup looping over the list
+                static const int slots = resident_slots(sift_knn2_kernel<1, 4, 2, 128, false, 0, 0, true, true, true>, 256);
+                const int grid2 = std::min(n_work << 2, full_row_grid(2 * (slots > 0 ? slots : SIFT_FULL_ROW_SLOTS)));
+                sift_knn2_kernel<1, 4, 2, 128, false, 0, 0, true, true, true><<<grid2, 256, 0, st>>>(
                     work2, pairs, imgs, desc8, norm, keyc, nullptr, nullptr, nullptr, nullptr, ratio, qlist, qcount2, work2_n,
                     top2, qlist2);
                 return hipGetLastError();

@@ -419,11 +419,12 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
     // List path: the product SIFT path (FP6 screen, exact pass 2 over the certified subset or every row, one
     // batch) and its predecessors (SIFT_VARIANT_FP6_FULL: every row for every forwarded query;
     // SIFT_VARIANT_INT8_LISTS: int8 screen, subset pass 2; SIFT_VARIANT_FP6_OTHER_SHAPE: the product path with the
-    // screen's other MFMA shape).  Every other diagnostic variant and
+    // screen's other MFMA shape; SIFT_VARIANT_FP6_SUBSET_WG: the product path with the certified route on
+    // sift_subset_kernel).  Every other diagnostic variant and
     // ORB keep the dense per-query arrays; fp32-fallback pairs of a list run do too, per pair.
     const bool lists = m->norm == SFMX_NORM_L2 &&
                        (variant_key == 0 || variant_key == SIFT_VARIANT_INT8_LISTS || variant_key == SIFT_VARIANT_FP6_FULL ||
-                        variant_key == SIFT_VARIANT_FP6_OTHER_SHAPE) &&
+                        variant_key == SIFT_VARIANT_FP6_OTHER_SHAPE || variant_key == SIFT_VARIANT_FP6_SUBSET_WG) &&
                        pass2_variant() == 10 && nb_want == 1 &&
                        !persist_screens();
     const bool reuse = m->plan_valid && m->plan_variant == variant_key && m->plan_imgs == img_key && m->plan_nb == nb_want &&
