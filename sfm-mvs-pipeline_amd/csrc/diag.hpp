@@ -6,8 +6,16 @@
 // The diagnostic build (`make diag` -> lib/libsfmx_diag.so, -DSFMX_DIAG) reads
 // them: A/B timing of kernel variants, the variant parity tests
 // (tests/diag.py loads that library next to the product one), and the
-// alternative BA factorization forms.  Variants that are timing probes with
-// wrong results exist only in that build.
+// alternative BA factorization forms.
+//
+// The matcher's switches (SFMX_SIFT_VARIANT, SFMX_SIFT_P2, SFMX_ORB_VARIANT,
+// SFMX_MATCH_BATCHES, SFMX_SCREEN_PERSIST, SFMX_FULL_ROW_GRID) are read in one
+// place, resolve_route of matcher.cpp, once per run, into a MatchRoute
+// (match_common.hpp) that the run plan keeps and the launchers receive; a
+// value it does not list fails the run with SFMX_EINVAL.  The kernels and
+// launch sequences only a non-product route reaches are in match_diag.hip,
+// which is empty without -DSFMX_DIAG; kernel templates both libraries
+// instantiate are in match_device.hpp.
 #pragma once
 
 // SFMX_SIFT_VARIANT value (diagnostic build) of the list path with the exact int8 screen and the subset
@@ -17,7 +25,7 @@ constexpr int SIFT_VARIANT_INT8_LISTS = 110;
 // for every forwarded query, the product path before the one-subset certificate: kept for the same uses.
 constexpr int SIFT_VARIANT_FP6_FULL = 111;
 // SFMX_SIFT_VARIANT value (diagnostic build) of the product path with the FP6 screen in the MFMA shape that
-// is not the product's (16 x 16 x 128 or 32 x 32 x 64, match_kernels.hip SIFT_SCREEN6_WIDE): kept for the same uses.
+// is not the product's (32 x 32 x 64, sift_screen6w_kernel of match_diag.hip; the product runs 16 x 16 x 128): kept for the same uses.
 constexpr int SIFT_VARIANT_FP6_OTHER_SHAPE = 112;
 // SFMX_SIFT_VARIANT value (diagnostic build) of the product path with the certified route's pass 2 on
 // sift_subset_kernel (one workgroup per pair and subset, rows staged in LDS), the product path before

@@ -11,11 +11,13 @@
 //   run         = the OpenMP pair loop (:40-88) as one batched launch sequence
 //   fetch       = the vector<ShotMatches> hand-back, as packed DMatch lists
 // No CPU fallback: every numeric step runs in the HIP kernels of
-// match_kernels.hip; a missing/unsupported device returns SFMX_EDEVICE.
+// match_kernels.hip (the diagnostic library's other routes: match_diag.hip); a
+// missing/unsupported device returns SFMX_EDEVICE.
 #include <hip/hip_runtime.h>
 #include "diag.hpp"
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,49 +30,6 @@
 #include "../../include/sfmx.h"
 #include "match_common.hpp"
 #include "sift_fp6.hpp"
-
-namespace sfmx {
-hipError_t launch_prep_l2(const float*, int, int, int, int8_t*, int32_t*, int32_t*, int32_t*, int32_t*, hipStream_t);
-hipError_t launch_probe_xor80(int8_t*, int64_t, hipStream_t);
-hipError_t launch_mfma_forms(int, int, int, const int32_t*, const int32_t*, const float*, float*, float*, hipStream_t);
-hipError_t launch_publish_flags(const int32_t*, int, int32_t*, unsigned*, unsigned, hipStream_t);
-hipError_t launch_prep_l2_batch(const PrepImg*, int, int, int8_t*, int32_t*, int32_t*, int32_t*, int32_t*, uint32_t*, float*,
-                                int2*, int32_t*, hipStream_t);
-hipError_t launch_prep_f32(const float*, int, int, int, float*, hipStream_t);
-hipError_t launch_prep_hamming(const uint8_t*, int, int, int, uint8_t*, hipStream_t);
-hipError_t launch_sift_knn2(const WorkItem*, int, const PairDev*, const ImgDev*, const int8_t*, const int32_t*,
-                            const int32_t*, const int32_t*, int32_t*, int32_t*, int, const int32_t*, WorkItem*,
-                            int32_t*, int32_t*, float*, int2*, int32_t*, double, hipStream_t, hipEvent_t, int32_t*,
-                            unsigned long long*, unsigned long long*, bool, const uint32_t*, const float*, const int2*,
-                            const int32_t*);
-hipError_t launch_finish_lists(const PairRec*, int, const int32_t*, const int32_t*, const int32_t*, unsigned long long*,
-                               const unsigned long long*, int2*, int32_t*, const int8_t*, const int32_t*, const int32_t*,
-                               const float*, double, int, int, int, int, int64_t*, int32_t*, int64_t*, DMatchDev*, int32_t*,
-                               hipStream_t, hipEvent_t);
-bool persist_screens();
-hipError_t launch_sift_slow(const int2*, const int32_t*, const PairDev*, const ImgDev*, const int8_t*,
-                            const int32_t*, int32_t*, float*, double, hipStream_t);
-hipError_t launch_sift_f32(const WorkItem*, int, const PairDev*, const ImgDev*, const float*, int32_t*, float*,
-                           double, hipStream_t);
-hipError_t launch_orb_knn2(const WorkItem*, int, const PairDev*, const ImgDev*, const uint8_t*, int32_t*, float*,
-                           double, hipStream_t);
-hipError_t launch_prep_hamming_fp4(const uint8_t*, int, int, int, uint8_t*, int32_t*, hipStream_t);
-hipError_t launch_orb_mfma(const WorkItem*, int, const PairDev*, const ImgDev*, const uint8_t*, const int32_t*,
-                           int32_t*, int32_t*, int, const int32_t*, WorkItem*, int32_t*, int32_t*, float*, double,
-                           hipStream_t, hipEvent_t, int32_t*, unsigned long long*);
-int orb_variant();
-int match_batches();
-int pass2_variant();
-hipError_t launch_two_pass_overlap(bool, const MatchBatch*, int, const WorkItem*, const PairDev*, const ImgDev*,
-                                   const int8_t*, const int32_t*, const int32_t*, int32_t*, int32_t*, int, const int32_t*,
-                                   int32_t*, float*, int2*, int32_t*, double, hipStream_t, hipEvent_t, int32_t*,
-                                   unsigned long long*, unsigned long long*, const OverlapStreams&);
-hipError_t launch_selftest_sqrt(int64_t, uint32_t*, hipStream_t);
-int sift_variant();
-int sift_block_queries(int variant);
-hipError_t launch_assemble(const PairDev*, int, const ImgDev*, const int32_t*, const float*, int, int, int,
-                           int64_t*, int32_t*, int64_t*, DMatchDev*, int32_t*, hipStream_t);
-}  // namespace sfmx
 
 using namespace sfmx;
 
@@ -164,7 +123,7 @@ struct DeviceGuard {
 struct sfmx_matcher {
     int device = 0;
     int norm = 0;
-    bool orb_fp4 = false;   // ORB rows expanded to +-1 FP4 (MFMA path), else 32-byte rows (VALU path)
+    bool orb_fp4 = false;   // ORB rows expanded to +-1 FP4 (MFMA forms), else 32-byte rows (MatchRoute::ORB_VALU): set_images' route
     int n_imgs = 0;
     std::vector<ImgDev> imgs;
     int64_t total_rows = 0;
@@ -194,15 +153,14 @@ struct sfmx_matcher {
     int hflags_cap = 0;
     unsigned flag_seq = 0;
     // Run plan cache: the device pair/work lists of the last run stay valid while the
-    // pair list, the images' row counts and integrality and the kernel variant are unchanged.
+    // pair list, the images' row counts and integrality and the run's route are unchanged.
     std::vector<int32_t> plan_pairs;
     std::vector<int64_t> plan_imgs;
-    int plan_variant = -1;
+    MatchRoute plan_route;
     bool plan_valid = false;
     int64_t plan_dense = 0;
     size_t plan_nwork = 0, plan_nwork32 = 0;
     int plan_max_nt = 0, plan_max_nq = 0;
-    bool plan_lists = false;         // the run settles and assembles from the forwarded lists (product SIFT path)
     bool has_run = false;
     // per run: start, main kernel end, run end, pass-1 end; a ring of EV_RING sets (r06) so the timing
     // of every run of a loop is readable afterwards (sfmx_matcher_timing_history) without a host sync
@@ -212,9 +170,8 @@ struct sfmx_matcher {
     hipEvent_t* ev = evr[0];
     long long runs = 0;
     bool ev_recorded = false;
-    // overlapped two-pass matching (launch_two_pass_overlap): the plan's batches, two more streams
+    // overlapped two-pass matching (a route of more than one batch): the plan's batches, two more streams
     std::vector<MatchBatch> batches;
-    int plan_nb = 0;
     hipStream_t sx = nullptr, sp = nullptr;
     hipEvent_t ov_ev[3] = {nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> bev;
@@ -248,6 +205,140 @@ int check_device(int dev) {
     return SFMX_OK;
 }
 
+// The route of a run (MatchRoute).  The product library has one, from constants.  The diagnostic library reads
+// the matcher's switches here and nowhere else, per run (tests switch routes within one process):
+//   SFMX_SIFT_VARIANT   0 (product), SIFT_VARIANT_* of diag.hpp (110-113), 103 / 106 / 107 / 108 (int8 screens:
+//                       32x32x32, and 16x16x64 in three tilings), 100 / 30 / 31 (single pass)
+//   SFMX_SIFT_P2        10 (the route's own pass 2), or full-row GATHER items into the dense arrays behind an
+//                       int8 screen: 0 = 128 queries, 1 / 3 = 256 (2 x 4 and 4 x 2 waves), 4 = 512
+//   SFMX_ORB_VARIANT    0 (product), 1 (VALU, 32-byte rows), 4 / 5 / 7 / 9 (single pass), 12 / 13 / 14 (full-row pass 2)
+//   SFMX_MATCH_BATCHES  1..64 overlapped batches of the int8 SIFT / the ORB product kernels
+//   SFMX_SCREEN_PERSIST 1 = ticket-fed persistent screens
+//   SFMX_FULL_ROW_GRID  grid of the product path's full-row launch
+// A value not listed fails the run (SFMX_EINVAL) instead of timing some other kernel.
+#ifndef SFMX_DIAG
+int resolve_route(int, MatchRoute& r) {
+    r = MatchRoute{};
+    return SFMX_OK;
+}
+#else
+int resolve_route(int norm, MatchRoute& r) {
+    using R = MatchRoute;
+    r = R{};
+    const auto value = [](const char* name, int dflt, std::string& text) {
+        const char* e = SFMX_DIAG_ENV(name);
+        text = std::string(name) + "=" + (e ? e : "");
+        return e ? atoi(e) : dflt;
+    };
+    std::string t_sv, t_p2, t_ov, t_nb, t_grid, t_persist;
+    const int sv = value("SFMX_SIFT_VARIANT", 0, t_sv), p2 = value("SFMX_SIFT_P2", 10, t_p2);
+    const int ov = value("SFMX_ORB_VARIANT", 0, t_ov);
+    const int nb = std::max(1, std::min(64, value("SFMX_MATCH_BATCHES", 1, t_nb)));
+    const int grid = value("SFMX_FULL_ROW_GRID", INT_MIN, t_grid);
+    r.persist = value("SFMX_SCREEN_PERSIST", 0, t_persist) == 1;
+    const auto unknown = [](const std::string& text) { return fail(SFMX_EINVAL, "unknown or removed switch value " + text); };
+    if (norm != SFMX_NORM_L2) {
+        switch (ov) {
+        case 0: r.orb = R::ORB_SUBSET; break;
+        case 1: r.orb = R::ORB_VALU; break;
+        case 4: r.orb = R::ORB_SINGLE_32_W16; break;
+        case 5: r.orb = R::ORB_SINGLE_16; break;
+        case 7: r.orb = R::ORB_SINGLE_16_W8; break;
+        case 9: r.orb = R::ORB_SINGLE_32_MINW1; break;
+        case 12: r.orb = R::ORB_GATHER_512; break;
+        case 13: r.orb = R::ORB_GATHER_128; break;
+        case 14: r.orb = R::ORB_GATHER_256; break;
+        default: return unknown(t_ov);
+        }
+        r.batches = ov == 0 ? nb : 1;   // the overlapped form exists for the product kernels
+        return SFMX_OK;
+    }
+    r.full_row_grid = grid == INT_MIN ? 0 : std::max(1, grid);
+    bool fp6 = false;   // a route with a list form
+    switch (sv) {
+    case 0: fp6 = true; break;
+    case SIFT_VARIANT_INT8_LISTS: fp6 = true; r.screen = R::INT8_16; r.pass2 = R::SUBSET; break;
+    case SIFT_VARIANT_FP6_FULL: fp6 = true; r.pass2 = R::FULL_ROWS; break;
+    case SIFT_VARIANT_FP6_OTHER_SHAPE: fp6 = true; r.screen = R::FP6_32; break;
+    case SIFT_VARIANT_FP6_SUBSET_WG: fp6 = true; r.pass2 = R::SUBSET_CERT; break;
+    case 103: r.screen = R::INT8_32; break;
+    case 106: r.screen = R::INT8_16; break;
+    case 107: r.screen = R::INT8_16_S128; break;
+    case 108: r.screen = R::INT8_16_W8; break;
+    case 100: r.screen = R::NO_SCREEN; r.pass2 = R::SINGLE; break;
+    case 30: r.screen = R::NO_SCREEN; r.pass2 = R::SINGLE_MINW1; break;
+    case 31: r.screen = R::NO_SCREEN; r.pass2 = R::SINGLE_R01; break;
+    default: return unknown(t_sv);
+    }
+    if (p2 != 10 && p2 != 0 && p2 != 1 && p2 != 3 && p2 != 4) return unknown(t_p2);
+    r.sift_lists = fp6 && p2 == 10 && nb == 1 && !r.persist;
+    if (r.screen == R::NO_SCREEN || r.sift_lists) return SFMX_OK;
+    // two passes into the dense arrays: the list routes' screens give way to the int8 one
+    if (fp6) r.screen = R::INT8_16;
+    if (p2 == 10) {   // subset pass 2 behind the int8 screen with subset masks; overlapped batches for the r02 default
+        r.screen = R::INT8_16;
+        r.pass2 = R::SUBSET;
+        r.batches = sv == 0 ? nb : 1;
+    } else {
+        r.pass2 = R::GATHER;
+        r.p2_qt = p2 == 0 ? 1 : p2 == 1 ? 2 : 4;
+        r.p2_waves = p2 == 3 ? 2 : 4;
+    }
+    return SFMX_OK;
+}
+
+// Batches of the overlapped two-pass path: whole pairs in `order`, about n_work / nb items each.
+int plan_batches(sfmx_matcher* m, int nb, const std::vector<PairDev>& pd, const std::vector<int>& order,
+                 const std::vector<WorkItem>& work) {
+    m->batches.clear();
+    const int n_pairs = (int)order.size();
+    const int64_t per = ((int64_t)work.size() + nb - 1) / nb;
+    MatchBatch cur{0, 0, 0, 0};
+    size_t w = 0;
+    for (int i = 0; i < n_pairs; ++i) {
+        const int p = order[i];
+        const bool f32path = m->norm == SFMX_NORM_L2 && !(m->imgs[pd[p].left].integral && m->imgs[pd[p].right].integral);
+        int items = 0;
+        while (!f32path && w + items < work.size() && work[w + items].pair == p) ++items;
+        cur.nw += items;
+        cur.np += 1;
+        w += items;
+        if (cur.nw >= per && i + 1 < n_pairs && w < work.size()) {   // (trailing no-work pairs join the last batch)
+            m->batches.push_back(cur);
+            cur = MatchBatch{(int32_t)w, 0, i + 1, 0};
+        }
+    }
+    if (cur.np > 0) m->batches.push_back(cur);
+    if (w != work.size()) return fail(SFMX_EINTERNAL, "match batches do not cover the work list");
+    return SFMX_OK;
+}
+
+// The screen and pass 2 of any route: overlapped on the matcher's extra streams where the route has more than
+// one batch (and the plan cut the work into at least two), else the route's dispatcher.
+int launch_route_diag(sfmx_matcher* m, const MatchRoute& route, const MatchBufs& B, int n_work, int n_pairs, double ratio,
+                      hipStream_t st) {
+    const bool sift = m->norm == SFMX_NORM_L2;
+    if (route.batches > 1 && m->batches.size() >= 2 && n_work > 0) {
+        if (!m->sx) {
+            HIPCHK(hipStreamCreateWithFlags(&m->sx, hipStreamNonBlocking));
+            HIPCHK(hipStreamCreateWithFlags(&m->sp, hipStreamNonBlocking));
+            for (auto& e : m->ov_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        while (m->bev.size() < m->batches.size()) {
+            hipEvent_t e = nullptr;
+            HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            m->bev.push_back(e);
+        }
+        const OverlapStreams os{m->sx, m->sp, m->ov_ev[0], m->ov_ev[1], m->ov_ev[2], m->bev.data()};
+        HIPCHK(launch_two_pass_overlap(sift, m->batches.data(), (int)m->batches.size(), B, n_pairs, ratio, st, m->ev[3], os));
+        return SFMX_OK;
+    }
+    HIPCHK(sift ? launch_sift_diag(route, B, n_work, n_pairs, ratio, st, m->ev[3])
+                : launch_orb_diag(route, B, n_work, n_pairs, ratio, st, m->ev[3]));
+    return SFMX_OK;
+}
+#endif
+
 int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hipStream_t st, bool device_src) {
     if (m) m->flags_pending = m->run_spec = false;   // (a pending check of earlier images is moot now)
     if (!m || (n > 0 && !imgs) || n < 0) return fail(SFMX_EINVAL, "null matcher/images");
@@ -264,9 +355,11 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
             return fail(SFMX_EINVAL, "more than 2^18 - 1 descriptors in one image");
         if (imgs[i].rows > 0 && !imgs[i].data) return fail(SFMX_EINVAL, "null descriptor data");
     }
+    MatchRoute route;   // ORB: the row layout follows the route; run_impl checks its own route against it
+    if (int rc_ = resolve_route(norm, route)) return rc_;
     DeviceGuard g(m->device);
     m->norm = norm;
-    m->orb_fp4 = norm == SFMX_NORM_HAMMING && orb_variant() != 1;
+    m->orb_fp4 = norm == SFMX_NORM_HAMMING && route.orb != MatchRoute::ORB_VALU;
     m->n_imgs = n;
     m->imgs.assign(n, ImgDev{});
     m->has_run = false;
@@ -331,12 +424,15 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
     }
     for (int i = 0; i < n && norm != SFMX_NORM_L2; ++i) {
         const ImgDev& d = m->imgs[i];
-        if (m->orb_fp4)
-            HIPCHK(launch_prep_hamming_fp4((const uint8_t*)src[i], d.rows, imgs[i].cols, d.rows_pad,
-                                           m->desc8.as<uint8_t>() + d.row0 * SIFT_DIM, m->keyc.as<int32_t>() + d.row0, st));
-        else
+#ifdef SFMX_DIAG
+        if (!m->orb_fp4) {
             HIPCHK(launch_prep_hamming((const uint8_t*)src[i], d.rows, imgs[i].cols, d.rows_pad,
                                        m->desc8.as<uint8_t>() + d.row0 * ORB_BYTES, st));
+            continue;
+        }
+#endif
+        HIPCHK(launch_prep_hamming_fp4((const uint8_t*)src[i], d.rows, imgs[i].cols, d.rows_pad,
+                                       m->desc8.as<uint8_t>() + d.row0 * SIFT_DIM, m->keyc.as<int32_t>() + d.row0, st));
     }
     m->any_nonintegral = false;
     if (norm == SFMX_NORM_L2 && n > 0) {
@@ -388,10 +484,6 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
             }
         }
     }
-#ifdef SFMX_DIAG
-    if (norm == SFMX_NORM_L2 && SFMX_DIAG_ENV("SFMX_PROBE_XOR80"))   // timing probe only (wrong results)
-        HIPCHK(launch_probe_xor80(m->desc8.as<int8_t>(), (int64_t)row * SIFT_DIM, st));
-#endif
     if (n > 0) {
         if ((rc = m->stage_imgs.ensure(sizeof(ImgDev) * n))) return rc;
         std::memcpy(m->stage_imgs.p, m->imgs.data(), sizeof(ImgDev) * n);
@@ -409,26 +501,22 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
     if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return fail(SFMX_EINVAL, "bad pair list");
     if (!(ratio == ratio)) return fail(SFMX_EINVAL, "ratio is NaN");
     DeviceGuard g(m->device);
+    MatchRoute route;
+    if (int rc_ = resolve_route(m->norm, route)) return rc_;
+    const bool sift = m->norm == SFMX_NORM_L2;
+#ifdef SFMX_DIAG
+    if (!sift && m->orb_fp4 != (route.orb != MatchRoute::ORB_VALU))   // the layout is set_images' decision
+        return fail(SFMX_EINVAL, "SFMX_ORB_VARIANT selects the other descriptor row layout than at set_images");
+#endif
+    // List path: the product SIFT path and its predecessors (resolve_route).  ORB and every other diagnostic
+    // route keep the dense per-query arrays; fp32-fallback pairs of a list run do too, per pair.
+    const bool lists = sift && route.sift_lists;
     // Run plan: per-pair dense offsets, the pair order by train image and the work
     // items.  Reused (no host work, no uploads) while the pair list, the images'
-    // row counts / integrality and the kernel variant are those of the last run.
-    const int variant_key = m->norm == SFMX_NORM_L2 ? sift_variant() : 0;
+    // row counts / integrality and the route are those of the last run.
     std::vector<int64_t> img_key(2 * (size_t)m->n_imgs);
     for (int i = 0; i < m->n_imgs; ++i) { img_key[2 * i] = m->imgs[i].rows; img_key[2 * i + 1] = m->imgs[i].integral; }
-    const int nb_want = match_batches();
-    // List path: the product SIFT path (FP6 screen, exact pass 2 over the certified subset or every row, one
-    // batch) and its predecessors (SIFT_VARIANT_FP6_FULL: every row for every forwarded query;
-    // SIFT_VARIANT_INT8_LISTS: int8 screen, subset pass 2; SIFT_VARIANT_FP6_OTHER_SHAPE: the product path with the
-    // screen's other MFMA shape; SIFT_VARIANT_FP6_SUBSET_WG: the product path with the certified route on
-    // sift_subset_kernel).  Every other diagnostic variant and
-    // ORB keep the dense per-query arrays; fp32-fallback pairs of a list run do too, per pair.
-    const bool lists = m->norm == SFMX_NORM_L2 &&
-                       (variant_key == 0 || variant_key == SIFT_VARIANT_INT8_LISTS || variant_key == SIFT_VARIANT_FP6_FULL ||
-                        variant_key == SIFT_VARIANT_FP6_OTHER_SHAPE || variant_key == SIFT_VARIANT_FP6_SUBSET_WG) &&
-                       pass2_variant() == 10 && nb_want == 1 &&
-                       !persist_screens();
-    const bool reuse = m->plan_valid && m->plan_variant == variant_key && m->plan_imgs == img_key && m->plan_nb == nb_want &&
-                       m->plan_lists == lists &&
+    const bool reuse = m->plan_valid && m->plan_route == route && m->plan_imgs == img_key &&
                        m->plan_pairs.size() == 2 * (size_t)n_pairs &&
                        (n_pairs == 0 || std::memcmp(m->plan_pairs.data(), pairs, sizeof(int32_t) * 2 * n_pairs) == 0);
     int rc;
@@ -457,10 +545,10 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
             const ImgDev& R = m->imgs[pd[p].right];
             max_nt = std::max(max_nt, R.rows);
             max_nq = std::max(max_nq, L.rows);
-            const bool f32path = m->norm == SFMX_NORM_L2 && !(L.integral && R.integral);
+            const bool f32path = sift && !(L.integral && R.integral);
             m->fp32_pairs += f32path;
             if (lists) recs.push_back(PairRec{L.row0, R.row0, pd[p].dense_base, L.rows, R.rows, R.rows_pad, p, f32path ? 0 : 1, 0});
-            const int bq = f32path ? 512 : (m->norm == SFMX_NORM_L2 ? sift_block_queries(sift_variant()) : 512);
+            const int bq = f32path ? 512 : route.block_queries;
             for (int q0 = 0; q0 < L.rows; q0 += bq) (f32path ? work32 : work).push_back(WorkItem{p, q0});
         }
         if ((rc = m->pairs_d.ensure(sizeof(PairDev) * std::max(n_pairs, 1)))) return rc;
@@ -503,37 +591,17 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
         if (!work32.empty()) HIPCHK(hipMemcpyAsync(m->work32_d.p, hs + b_pd + b_or + b_w, sizeof(WorkItem) * work32.size(), hipMemcpyHostToDevice, st));
         if (!recs.empty()) HIPCHK(hipMemcpyAsync(m->recs.p, hs + b_pd + b_or + b_w + b_w32, b_rc, hipMemcpyHostToDevice, st));
         if ((rc = m->stage_run.copied(st))) return rc;
-        {   // batches of the overlapped two-pass path: whole pairs in `order`, about n_work / nb items each
-            m->batches.clear();
-            const int64_t per = ((int64_t)work.size() + nb_want - 1) / std::max(nb_want, 1);
-            MatchBatch cur{0, 0, 0, 0};
-            size_t w = 0;
-            for (int i = 0; i < n_pairs; ++i) {
-                const int p = order[i];
-                const bool f32path = m->norm == SFMX_NORM_L2 && !(m->imgs[pd[p].left].integral && m->imgs[pd[p].right].integral);
-                int items = 0;
-                while (!f32path && w + items < work.size() && work[w + items].pair == p) ++items;
-                cur.nw += items;
-                cur.np += 1;
-                w += items;
-                if (cur.nw >= per && i + 1 < n_pairs && w < work.size()) {   // (trailing no-work pairs join the last batch)
-                    m->batches.push_back(cur);
-                    cur = MatchBatch{(int32_t)w, 0, i + 1, 0};
-                }
-            }
-            if (cur.np > 0) m->batches.push_back(cur);
-            if (w != work.size()) return fail(SFMX_EINTERNAL, "match batches do not cover the work list");
-        }
-        m->plan_nb = nb_want;
+#ifdef SFMX_DIAG
+        if (route.batches > 1 && (rc = plan_batches(m, route.batches, pd, order, work))) return rc;
+#endif
         m->plan_pairs.assign(pairs, pairs + 2 * (size_t)n_pairs);
         m->plan_imgs = img_key;
-        m->plan_variant = variant_key;
+        m->plan_route = route;
         m->plan_dense = dense;
         m->plan_nwork = work.size();
         m->plan_nwork32 = work32.size();
         m->plan_max_nt = max_nt;
         m->plan_max_nq = max_nq;
-        m->plan_lists = lists;
         m->plan_valid = true;
     }
     const int64_t dense = m->plan_dense;
@@ -551,86 +619,53 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
     HIPCHK(hipEventRecord(m->ev[3], st));   // re-recorded after pass 1 by the two-pass launchers
     // Pairs with an empty left image have no work item; pairs with an empty
     // right image are handled in-kernel (every query: no neighbour).
-    const PairDev* P = m->pairs_d.as<PairDev>();
-    const ImgDev* I = m->imgs_d.as<ImgDev>();
-    // overlapped two-pass product path (SIFT: the default screen + subset pass 2; ORB: FP4 screen + subset)
-    const bool overlap = m->batches.size() >= 2 && n_work > 0 &&
-                         ((m->norm == SFMX_NORM_L2 && sift_variant() == 0 && pass2_variant() == 10) ||
-                          (m->norm != SFMX_NORM_L2 && m->orb_fp4 && orb_variant() == 0));
-    OverlapStreams os{};
-    if (overlap) {
-        if (!m->sx) {
-            HIPCHK(hipStreamCreateWithFlags(&m->sx, hipStreamNonBlocking));
-            HIPCHK(hipStreamCreateWithFlags(&m->sp, hipStreamNonBlocking));
-            for (auto& e : m->ov_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
-        while (m->bev.size() < m->batches.size()) {
-            hipEvent_t e = nullptr;
-            HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            m->bev.push_back(e);
-        }
-        os = OverlapStreams{m->sx, m->sp, m->ov_ev[0], m->ov_ev[1], m->ov_ev[2], m->bev.data()};
-    }
-    if (overlap) {
-        const bool sift = m->norm == SFMX_NORM_L2;
-        HIPCHK(launch_two_pass_overlap(sift, m->batches.data(), (int)m->batches.size(), m->work_d.as<WorkItem>(), P, I,
-                                       m->desc8.as<int8_t>(), sift ? m->normv.as<int32_t>() : nullptr,
-                                       sift ? m->keyc2.as<int32_t>() : m->keyc.as<int32_t>(), m->qlist.as<int32_t>(),
-                                       m->qcount.as<int32_t>(), n_pairs, m->porder.as<int32_t>(),
-                                       m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), m->slow_list.as<int2>(),
-                                       m->slow_count.as<int32_t>(), ratio, st, m->ev[3], m->qmask.as<int32_t>(),
-                                       m->top2.as<unsigned long long>(), m->out.as<unsigned long long>(), os));
-        HIPCHK(hipEventRecord(m->ev[1], st));
-        if (sift) {
-            HIPCHK(launch_sift_slow(m->slow_list.as<int2>(), m->slow_count.as<int32_t>(), P, I, m->desc8.as<int8_t>(),
-                                    m->normv.as<int32_t>(), m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), ratio, st));
-            if (n_work32)
-                HIPCHK(launch_sift_f32(m->work32_d.as<WorkItem>(), (int)n_work32, P, I, m->f32.as<float>(),
-                                       m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), ratio, st));
-        }
-    } else if (m->norm == SFMX_NORM_L2) {
-        HIPCHK(launch_sift_knn2(m->work_d.as<WorkItem>(), (int)n_work, P, I, m->desc8.as<int8_t>(),
-                                m->normv.as<int32_t>(), m->keyc.as<int32_t>(), m->keyc2.as<int32_t>(),
-                                m->qlist.as<int32_t>(), m->qcount.as<int32_t>(), n_pairs, m->porder.as<int32_t>(),
-                                m->work2.as<WorkItem>(), m->work2_n.as<int32_t>(), m->dense_idx.as<int32_t>(),
-                                m->dense_dist.as<float>(), m->slow_list.as<int2>(), m->slow_count.as<int32_t>(), ratio, st,
-                                m->ev[3], m->qmask.as<int32_t>(), m->top2.as<unsigned long long>(),
-                                m->out.as<unsigned long long>(),   // pass 2's second slot: `out` is idle until assembly
-                                m->plan_lists, m->desc6.as<uint32_t>(), m->keyf.as<float>(), m->ne.as<int2>(),
-                                m->imax.as<int32_t>()));
-        if (!m->plan_lists) {
-            HIPCHK(hipEventRecord(m->ev[1], st));
-            HIPCHK(launch_sift_slow(m->slow_list.as<int2>(), m->slow_count.as<int32_t>(), P, I, m->desc8.as<int8_t>(),
-                                    m->normv.as<int32_t>(), m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), ratio, st));
-        }
-        if (n_work32)
-            HIPCHK(launch_sift_f32(m->work32_d.as<WorkItem>(), (int)n_work32, P, I, m->f32.as<float>(),
-                                   m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), ratio, st));
-    } else if (m->orb_fp4) {
-        HIPCHK(launch_orb_mfma(m->work_d.as<WorkItem>(), (int)n_work, P, I, m->desc8.as<uint8_t>(),
-                               m->keyc.as<int32_t>(), m->qlist.as<int32_t>(), m->qcount.as<int32_t>(), n_pairs,
-                               m->porder.as<int32_t>(), m->work2.as<WorkItem>(), m->work2_n.as<int32_t>(),
-                               m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), ratio, st, m->ev[3],
-                               m->qmask.as<int32_t>(), m->top2.as<unsigned long long>()));
-        HIPCHK(hipEventRecord(m->ev[1], st));
-    } else {
-        HIPCHK(launch_orb_knn2(m->work_d.as<WorkItem>(), (int)n_work, P, I, m->desc8.as<uint8_t>(),
-                               m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), ratio, st));
-        HIPCHK(hipEventRecord(m->ev[1], st));
-    }
-    const int max_nt = m->plan_max_nt;
-    if (m->plan_lists)   // settle + count (ev[1] behind it), scan, write: the writer of `out` runs after slot1's last reader
-        HIPCHK(launch_finish_lists(m->recs.as<PairRec>(), n_pairs, m->qlist.as<int32_t>(), m->qmask.as<int32_t>(),
-                                   m->qcount.as<int32_t>(), m->top2.as<unsigned long long>(),
-                                   m->out.as<unsigned long long>(), m->slow_list.as<int2>(), m->slow_count.as<int32_t>(),
-                                   m->desc8.as<int8_t>(), m->normv.as<int32_t>(), m->dense_idx.as<int32_t>(),
-                                   m->dense_dist.as<float>(), ratio, distinct ? 1 : 0, min_count, m->plan_max_nq, max_nt,
-                                   m->counts.as<int64_t>(), m->keep.as<int32_t>(), m->offsets.as<int64_t>(),
-                                   m->out.as<DMatchDev>(), m->unsettled.as<int32_t>(), st, m->ev[1]));
+    MatchBufs B{};
+    B.work = m->work_d.as<WorkItem>();
+    B.work32 = m->work32_d.as<WorkItem>();
+    B.pairs = m->pairs_d.as<PairDev>();
+    B.imgs = m->imgs_d.as<ImgDev>();
+    B.porder = m->porder.as<int32_t>();
+    B.recs = m->recs.as<PairRec>();
+    B.desc8 = m->desc8.as<int8_t>();
+    B.norm = m->normv.as<int32_t>();
+    B.keyc = m->keyc.as<int32_t>();
+    B.keyc2 = m->keyc2.as<int32_t>();
+    B.desc6 = m->desc6.as<uint32_t>();
+    B.keyf = m->keyf.as<float>();
+    B.ne = m->ne.as<int2>();
+    B.imax = m->imax.as<int32_t>();
+    B.f32 = m->f32.as<float>();
+    B.qlist = m->qlist.as<int32_t>();
+    B.qcount = m->qcount.as<int32_t>();
+    B.qmask = m->qmask.as<int32_t>();
+    B.top2 = m->top2.as<unsigned long long>();
+    B.slot1 = m->out.as<unsigned long long>();   // pass 2's second slot: `out` is idle until assembly
+    B.work2 = m->work2.as<WorkItem>();
+    B.work2_n = m->work2_n.as<int32_t>();
+    B.dense_idx = m->dense_idx.as<int32_t>();
+    B.dense_dist = m->dense_dist.as<float>();
+    B.slow_list = m->slow_list.as<int2>();
+    B.slow_count = m->slow_count.as<int32_t>();
+    B.unsettled = m->unsettled.as<int32_t>();
+    B.counts = m->counts.as<int64_t>();
+    B.keep = m->keep.as<int32_t>();
+    B.offsets = m->offsets.as<int64_t>();
+    B.out = m->out.as<DMatchDev>();
+#ifdef SFMX_DIAG
+    if ((rc = launch_route_diag(m, route, B, (int)n_work, n_pairs, ratio, st))) return rc;
+#else
+    HIPCHK(sift ? launch_sift_product(B, (int)n_work, n_pairs, ratio, route.full_row_grid, st, m->ev[3])
+                : launch_orb_product(B, (int)n_work, n_pairs, ratio, st, m->ev[3]));
+#endif
+    if (!lists) HIPCHK(hipEventRecord(m->ev[1], st));
+#ifdef SFMX_DIAG
+    if (sift && !lists) HIPCHK(launch_sift_slow(B, ratio, st));
+#endif
+    if (n_work32) HIPCHK(launch_sift_f32(B, (int)n_work32, ratio, st));
+    if (lists)   // settle + count (ev[1] behind it), scan, write: the writer of `out` runs after slot1's last reader
+        HIPCHK(launch_finish_lists(B, n_pairs, ratio, distinct ? 1 : 0, min_count, m->plan_max_nq, m->plan_max_nt, st, m->ev[1]));
     else
-        HIPCHK(launch_assemble(P, n_pairs, I, m->dense_idx.as<int32_t>(), m->dense_dist.as<float>(), distinct ? 1 : 0,
-                               min_count, max_nt, m->counts.as<int64_t>(), m->keep.as<int32_t>(),
-                               m->offsets.as<int64_t>(), m->out.as<DMatchDev>(), m->unsettled.as<int32_t>(), st));
+        HIPCHK(launch_assemble(B, n_pairs, distinct ? 1 : 0, min_count, m->plan_max_nt, st));
     HIPCHK(hipEventRecord(m->ev[2], st));
     m->ev_recorded = true;
     m->n_pairs = n_pairs;

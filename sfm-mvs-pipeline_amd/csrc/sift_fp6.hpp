@@ -1,6 +1,6 @@
 // SPDX-License-Identifier: MIT
 // Conservative FP6 (e2m3) first pass of the exact SIFT matcher: the quantiser, the packed row layout
-// and the bound arithmetic, for the device (match_kernels.hip) and for the host (tests/cpp/sift_fp6_main.cpp,
+// and the bound arithmetic, for the device (match_device.hpp) and for the host (tests/cpp/sift_fp6_main.cpp,
 // tests/test_sift_fp6_bound.py restates it in numpy; the one-subset certificate: tests/cpp/sift_fp6_cert_main.cpp,
 // tests/test_sift_fp6_cert.py).  No HIP header is needed to compile it for the host.
 //
