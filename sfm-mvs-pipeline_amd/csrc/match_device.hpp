@@ -390,6 +390,70 @@ struct Screen6Stage {
     }
 };
 
+// The read-ahead of sift_screen6_kernel's row loop.  A 32-row block of a stage in registers: per 16-row block the
+// lane's plane-A piece (16 B: lo), its plane-B piece (8 B: hi) and the four keys of its accumulator rows (k).
+// Two such sets take turns, each in registers of its own named here: lo and hi of a 16-row block are adjacent (the
+// MFMA takes them as one 192-bit operand), and a set that the allocator places itself costs copies at the stage
+// seam, where the first block of the next stage is requested while the other set is still to be multiplied.
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+#define SCREEN6_REGS_0(C) C "{v[120:123]}"(lo0), C "{v[124:125]}"(hi0), C "{v[132:135]}"(k0), C "{v[126:129]}"(lo1), C "{v[130:131]}"(hi1), C "{v[136:139]}"(k1)
+#define SCREEN6_REGS_1(C) C "{v[140:143]}"(lo0), C "{v[144:145]}"(hi0), C "{v[152:155]}"(k0), C "{v[146:149]}"(lo1), C "{v[150:151]}"(hi1), C "{v[156:159]}"(k1)
+// Requests block T of the stage at the lane's bases (plane A, plane B, keys; LDS byte addresses) into set SET: six
+// reads the compiler does not count and does not drain the LDS-DMA in front of.  The registers hold the block
+// only after screen6_arrived.
+template <int SET, int T>
+__device__ __forceinline__ void screen6_request(i32x4& lo0, i32x2& hi0, f32x4& k0, i32x4& lo1, i32x2& hi1, f32x4& k1,
+                                                unsigned pa, unsigned pb, unsigned pk) {
+#define SCREEN6_REQUEST(REGS)                                                                                           \
+    asm volatile("ds_read_b128 %0, %6 offset:%9\n\t"                                                                    \
+                 "ds_read_b64 %1, %7 offset:%10\n\t"                                                                    \
+                 "ds_read_b128 %2, %8 offset:%11\n\t"                                                                   \
+                 "ds_read_b128 %3, %6 offset:%12\n\t"                                                                   \
+                 "ds_read_b64 %4, %7 offset:%13\n\t"                                                                    \
+                 "ds_read_b128 %5, %8 offset:%14"                                                                        \
+                 : REGS("=")                                                                                            \
+                 : "v"(pa), "v"(pb), "v"(pk), "n"(2 * T * 1024), "n"(2 * T * 512), "n"(2 * T * 64),                      \
+                   "n"((2 * T + 1) * 1024), "n"((2 * T + 1) * 512), "n"((2 * T + 1) * 64)                                \
+                 : "memory")
+    if constexpr (SET == 0) SCREEN6_REQUEST(SCREEN6_REGS_0);
+    else SCREEN6_REQUEST(SCREEN6_REGS_1);
+#undef SCREEN6_REQUEST
+}
+// Waits until at most N LDS reads are in flight (they return in order) and hands set SET to the compiler: nothing
+// that reads it is scheduled above the wait.
+template <int SET, int N>
+__device__ __forceinline__ void screen6_arrived(i32x4& lo0, i32x2& hi0, f32x4& k0, i32x4& lo1, i32x2& hi1, f32x4& k1) {
+    if constexpr (SET == 0) asm volatile("s_waitcnt lgkmcnt(%6)" : SCREEN6_REGS_0("+") : "n"(N));
+    else asm volatile("s_waitcnt lgkmcnt(%6)" : SCREEN6_REGS_1("+") : "n"(N));
+}
+// A block's MFMAs and folds over the wave's QT query tiles: e2m3 for both operands, the unit-scale product
+// (fp6::mfma16), the keys as C, v_max3_f32 into the four chains of a tile.  A fence on both sides keeps them
+// between the request in front and the wait behind; inside, a tile's four folds follow the next tile's two MFMAs,
+// so two result pairs are live at a time.  (In the compiler's own order four pairs are, and the second register
+// set does not fit beside them at three waves per SIMD.)
+template <int QT>
+__device__ __forceinline__ void screen6_mul(const i32x8 (&bq)[QT], float (&ch)[QT][4], i32x4 lo0, i32x2 hi0, f32x4 k0,
+                                            i32x4 lo1, i32x2 hi1, f32x4 k1) {
+    __builtin_amdgcn_sched_barrier(0);
+    const i32x8 a0 = i32x8{lo0.x, lo0.y, lo0.z, lo0.w, hi0.x, hi0.y, 0, 0};
+    const i32x8 a1 = i32x8{lo1.x, lo1.y, lo1.z, lo1.w, hi1.x, hi1.y, 0, 0};
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+        const f32x4 acc0 = fp6::mfma16<fp6::FMT_E2M3, false>(a0, bq[qt], k0);
+        const f32x4 acc1 = fp6::mfma16<fp6::FMT_E2M3, false>(a1, bq[qt], k1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ch[qt][i] = fmaxf(fmaxf(ch[qt][i], acc0[i]), acc1[i]);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
+#pragma unroll
+    for (int qt = 1; qt < QT; ++qt) {
+        __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x2, 4, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x2, 4, 0);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // ---------------------------------------------------------------------------
 // Screening pass of the product path on the FP6 matrix pipe: v_mfma_f32_16x16x128_f8f6f4 (unscaled, fp6::mfma16) with e2m3
 // operands, one MFMA (K = 128) per 16 x 16 tile, twice the MACs per clock of the int8 screens.  The
@@ -454,46 +518,54 @@ void sift_screen6_kernel(const WorkItem* __restrict__ work, const PairDev* __res
     // The lane's LDS reads: row block (t, b) is rows 16 (2 t + b) + l16, and the swizzles have a period of 16 rows,
     // so a lane reads at three bases computed once (plane A, plane B, keys) plus a compile-time offset per
     // buffer and row block, which goes into the ds_read offset field.
-    const char* ra = lds + l16 * 64 + 16 * (g ^ fp6::swz_a(l16));
-    const char* rb = lds + A_BYTES + l16 * 32 + 16 * ((g >> 1) ^ fp6::swz_b(l16)) + 8 * (g & 1);
-    const char* rk = lds + A_BYTES + B_BYTES + 16 * g;
+    const unsigned lds0 = (unsigned)(size_t)(LDS_AS const void*)lds;
+    const unsigned ra = lds0 + l16 * 64 + 16 * (g ^ fp6::swz_a(l16));
+    const unsigned rb = lds0 + A_BYTES + l16 * 32 + 16 * ((g >> 1) ^ fp6::swz_b(l16)) + 8 * (g & 1);
+    const unsigned rk = lds0 + A_BYTES + B_BYTES + 16 * g;
     static_assert(fp6::swz_a(16) == fp6::swz_a(0) && fp6::swz_b(16) == fp6::swz_b(0), "swizzle period of 16 rows");
+    static_assert(STAGE == 128, "the row loop is written out for four 32-row blocks per stage");
+
+    // The row loop runs one 32-row block ahead: block n + 1's six reads are requested into the other register
+    // set before block n's sixteen MFMAs, and the wait in front of a block's MFMAs is counted (LDS reads return
+    // in order, so lgkmcnt(6) with the next block's six in flight means this block's have landed).
+#define SCREEN6_SET0 lo00, hi00, k00, lo01, hi01, k01
+#define SCREEN6_SET1 lo10, hi10, k10, lo11, hi11, k11
 
     if (nstages > 0) stager.issue(lds, 0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    i32x4 lo00, lo01, lo10, lo11;
+    i32x2 hi00, hi01, hi10, hi11;
+    f32x4 k00, k01, k10, k11;
+    unsigned pa = ra, pb = rb, pk = rk;
+    screen6_request<0, 0>(SCREEN6_SET0, pa, pb, pk);
     for (int s = 0; s < nstages; ++s) {
-        const int buf = s & 1;
-        if (s + 1 < nstages) stager.issue(lds, s + 1, buf ^ 1);
-        // the buffer select is wave-uniform: one add per base and stage
-        const char *pa = ra + buf * BUF_BYTES, *pb = rb + buf * BUF_BYTES, *pk = rk + buf * BUF_BYTES;
-#pragma unroll
-        for (int t = 0; t < STAGE / 32; ++t) {
-            i32x8 a[2];
-            f32x4 cinit[2];
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const int blk = 2 * t + b;   // 16-row block of the stage
-                const i32x4 lo = *reinterpret_cast<const i32x4*>(pa + blk * 16 * 64);
-                // (volatile: one ds_read_b64 per fragment.  Merged into ds_read2st64_b64, the two row blocks' halves
-                // land in one register quad and cost four v_mov_b32 per 32 rows to reach their fragments.)
-                const long long hi = *(const volatile LDS_AS long long*)(pb + blk * 16 * 32);
-                a[b] = i32x8{lo.x, lo.y, lo.z, lo.w, (int)hi, (int)(hi >> 32), 0, 0};
-                cinit[b] = *reinterpret_cast<const f32x4*>(pk + blk * 16 * 4);
-            }
-#pragma unroll
-            for (int qt = 0; qt < QT; ++qt) {
-                // e2m3 for both operands, the unit-scale product (fp6::mfma16)
-                const f32x4 acc0 = fp6::mfma16<fp6::FMT_E2M3, false>(a[0], bq[qt], cinit[0]);
-                const f32x4 acc1 = fp6::mfma16<fp6::FMT_E2M3, false>(a[1], bq[qt], cinit[1]);
-                // (folding one tile behind, the folds pinned under the next tile's MFMAs, measured slower: DESIGN 5)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) ch[qt][i] = fmaxf(fmaxf(ch[qt][i], acc0[i]), acc1[i]);
-            }
-        }
+        // every wave has read stage s - 1 (the barrier below), so stage s + 1 may land in its buffer; the branch
+        // stands at the top so that the body below is one basic block
+        if (s + 1 < nstages) stager.issue(lds, s + 1, (s + 1) & 1);
+        screen6_request<1, 1>(SCREEN6_SET1, pa, pb, pk);
+        screen6_arrived<0, 6>(SCREEN6_SET0);
+        screen6_mul<QT>(bq, ch, SCREEN6_SET0);
+        screen6_request<0, 2>(SCREEN6_SET0, pa, pb, pk);
+        screen6_arrived<1, 6>(SCREEN6_SET1);
+        screen6_mul<QT>(bq, ch, SCREEN6_SET1);
+        screen6_request<1, 3>(SCREEN6_SET1, pa, pb, pk);
+        screen6_arrived<0, 6>(SCREEN6_SET0);
+        screen6_mul<QT>(bq, ch, SCREEN6_SET0);
+        // Stage end: the last block's operands are in registers before the barrier, the next stage's first block
+        // is requested from the other buffer straight after it, and the last block's MFMAs run under that read.
+        screen6_arrived<1, 0>(SCREEN6_SET1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        // the buffer select is wave-uniform: one add per base and stage
+        const int nb = s & 1 ? -BUF_BYTES : BUF_BYTES;
+        pa += nb; pb += nb; pk += nb;
+        screen6_request<0, 0>(SCREEN6_SET0, pa, pb, pk);   // (behind the last stage: the other buffer's old rows, never multiplied)
+        screen6_mul<QT>(bq, ch, SCREEN6_SET1);
     }
+    screen6_arrived<0, 0>(SCREEN6_SET0);   // no read in flight into registers the epilogue reuses
+#undef SCREEN6_SET0
+#undef SCREEN6_SET1
 
     const int emax2 = imax[2 * P.right], amax2 = imax[2 * P.right + 1];
     // After the two shuffle rounds every lane group holds a tile's (k1, k2, r1), so lane group g decides tile

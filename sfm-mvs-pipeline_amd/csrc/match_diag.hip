@@ -1207,7 +1207,7 @@ hipError_t launch_sift_diag(const MatchRoute& r, const MatchBufs& b, int n_work,
                 sift_screen6w_kernel<4, 2, 128, true><<<n_work, 256, 0, st>>>(b.work, b.pairs, b.imgs, b.desc6, b.keyf, b.ne, b.imax,
                                                                              b.qlist, b.qcount, ratio, b.qmask, b.top2, qlist2, qcount2);
             else
-                sift_screen6_kernel<8, 4, 2, 128, true><<<n_work, 256, 0, st>>>(b.work, b.pairs, b.imgs, b.desc6, b.keyf, b.ne, b.imax,
+                sift_screen6_kernel<8, 4, 3, 128, true><<<n_work, 256, 0, st>>>(b.work, b.pairs, b.imgs, b.desc6, b.keyf, b.ne, b.imax,
                                                                                b.qlist, b.qcount, ratio, b.qmask, b.top2, qlist2, qcount2);
             RECORD_SCREEN();
             if (r.pass2 == R::SUBSET_CERT)
@@ -1218,7 +1218,7 @@ hipError_t launch_sift_diag(const MatchRoute& r, const MatchBufs& b, int n_work,
                                                                  b.porder, b.top2);
             return launch_sift_full_rows(b, n_work, n_pairs, ratio, r.full_row_grid, st);
         case R::FULL_ROWS:     // FP6 screen, exact pass 2 over every train row for every forwarded query (SIFT_VARIANT_FP6_FULL)
-            sift_screen6_kernel<8, 4, 2, 128, false><<<n_work, 256, 0, st>>>(b.work, b.pairs, b.imgs, b.desc6, b.keyf, b.ne, b.imax,
+            sift_screen6_kernel<8, 4, 3, 128, false><<<n_work, 256, 0, st>>>(b.work, b.pairs, b.imgs, b.desc6, b.keyf, b.ne, b.imax,
                                                                             b.qlist, b.qcount, ratio, b.qmask, b.top2, nullptr, nullptr);
             RECORD_SCREEN();
             compact_work_kernel<7><<<1, 1024, 0, st>>>(b.porder, n_pairs, b.qcount, b.work2, b.work2_n);

@@ -798,7 +798,7 @@ hipError_t launch_sift_product(const MatchBufs& b, int n_work, int n_pairs, doub
     if (n_work == 0) return hipSuccess;
     int32_t* qlist2 = reinterpret_cast<int32_t*>(b.slot1);
     int32_t* qcount2 = b.qcount + arena_qcount2(n_pairs);
-    sift_screen6_kernel<8, 4, 2, 128, true><<<n_work, 256, 0, st>>>(b.work, b.pairs, b.imgs, b.desc6, b.keyf, b.ne, b.imax,
+    sift_screen6_kernel<8, 4, 3, 128, true><<<n_work, 256, 0, st>>>(b.work, b.pairs, b.imgs, b.desc6, b.keyf, b.ne, b.imax,
                                                                    b.qlist, b.qcount, ratio, b.qmask, b.top2, qlist2, qcount2);
     if (ev_screen) {
         const hipError_t e = hipEventRecord(ev_screen, st);
