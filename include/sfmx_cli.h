@@ -59,6 +59,8 @@ int32_t sfmx_args_is_flag(const sfmx_args* a, const char* key);
 int64_t sfmx_args_to_string(const sfmx_args* a, char* buf, int64_t cap);
 
 /* ---- PhotogrammetrieCli configuration ------------------------------------ */
+/* Run modes of App::main.  PCL_STATS reads only -Pinput / -Pstats / -Pneighbors /
+ * -Pquality (PclStatsCli.cpp:30-65; include/sfmx_cloud.h does the work). */
 enum { SFMX_RUN_HELP = 0, SFMX_RUN_PHOTOGRAMMETRIE = 1, SFMX_RUN_PCL_STATS = 2 };
 enum { SFMX_DETECTOR_SIFT = 0, SFMX_DETECTOR_ORB = 1 };
 /* FLANN is recorded as requested; sfmx executes every matcher as exact BF
@@ -120,8 +122,9 @@ typedef struct sfmx_cli_config {
  * the flag; the config then holds the values read before it. */
 int sfmx_cli_configure(const sfmx_args* a, sfmx_cli_config* cfg, char* log, int64_t log_cap, int64_t* log_len);
 
-/* Usage text of App (which = 0) or of the photogrammetrie sub-program (1), with
- * the defaults the code applies.  String result as above. */
+/* Usage text of App (which = 0), of the photogrammetrie sub-program (1) or of
+ * the pcl-stats sub-program (2; PclStatsCli.cpp:67-79), with the defaults the
+ * code applies.  String result as above. */
 int64_t sfmx_cli_usage(const char* exec_name, int32_t which, char* buf, int64_t cap);
 
 #ifdef __cplusplus

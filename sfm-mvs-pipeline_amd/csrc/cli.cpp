@@ -355,8 +355,15 @@ int64_t sfmx_cli_usage(const char* exec_name, int32_t which, char* buf, int64_t 
             "\n\t --stats (write run statistics)"
             "\n\t --artifacts (write intermediate artefacts)"
             "\n\t --help (this text)";
+    } else if (which == 2) {   // PclStatsCli::printUsage (PclStatsCli.cpp:67-79)
+        s = "usage: " + exe + " -Prun=pcl-stats"
+            "\n\t -Pinput=[input file; must be a PLY file] = pointcloud.ply"
+            "\n\t -Pstats=[output file of the statistics; a CSV file is written] (optional)"
+            "\n\t -Pneighbors=[output file of the neighbour histogram; a CSV file is written] (optional)"
+            "\n\t -Pquality=[output file of the quality PLY] (optional)"
+            "\n\t --help (this text)";
     } else {
-        sfmx::set_last_error("sfmx_cli_usage: which must be 0 or 1");
+        sfmx::set_last_error("sfmx_cli_usage: which must be 0, 1 or 2");
         return SFMX_EINVAL;
     }
     return put_string(s, buf, cap);

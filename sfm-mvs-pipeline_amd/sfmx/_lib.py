@@ -61,6 +61,12 @@ class sfmx_tri_camera(C.Structure):
     _fields_ = [("K", C.c_double * 9), ("dist", C.c_double * 5)]
 
 
+class sfmx_cloud_stats(C.Structure):
+    """include/sfmx_cloud.h"""
+    _fields_ = [("n_points", C.c_int64)] + [(n, C.c_double) for n in ("max", "min", "mean", "median", "variance",
+                                                                      "deviation")]
+
+
 class sfmx_ba_plan_info(C.Structure):
     _fields_ = [("order", C.c_int32), ("leaf_tiles", C.c_int32), ("npad", C.c_int32), ("tiles", C.c_int32),
                 ("tiles_nz", C.c_int32), ("height", C.c_int32), ("leaves", C.c_int32), ("tasks", C.c_int32),
@@ -95,7 +101,7 @@ class sfmx_cli_config(C.Structure):
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
 
-# Every symbol include/sfmx.h (and include/sfmx_ba.h, sfmx_homography.h, sfmx_triangulate.h, sfmx_pose.h, sfmx_pnp.h, sfmx_scene.h) declares, with its ctypes prototype.
+# Every symbol include/sfmx.h (and include/sfmx_ba.h, sfmx_homography.h, sfmx_triangulate.h, sfmx_pose.h, sfmx_pnp.h, sfmx_scene.h, sfmx_cloud.h) declares, with its ctypes prototype.
 _P = C.POINTER
 _i32p, _i64p, _vp = _P(C.c_int32), _P(C.c_int64), C.c_void_p
 PROTOTYPES = {
@@ -173,6 +179,14 @@ PROTOTYPES = {
                                              _vp, _vp, _vp, _vp, _vp, _vp, _i32p, _i64p]),
     "sfmx_merge_pointcloud_last_kernel_ms": (C.c_float, []),
     "sfmx_merge_pointcloud_last_stats": (C.c_int, [_i64p, _i64p, _i64p]),
+    "sfmx_cloud_neighbor_distances": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "sfmx_cloud_last_stats": (C.c_int, [_P(C.c_float), _i64p, _i64p]),
+    "sfmx_cloud_statistics": (C.c_int, [_vp, C.c_int64, C.c_int64, _P(sfmx_cloud_stats)]),
+    "sfmx_cloud_histogram": (C.c_int, [_vp, C.c_int64, C.c_double, _vp, _vp, C.c_int64, _i64p]),
+    "sfmx_ply_read": (C.c_int, [C.c_char_p, _vp, C.c_int64, _i64p, _vp, C.c_int64, _i64p, _vp, C.c_int64, _i64p]),
+    "sfmx_cloud_write_stats_csv": (C.c_int, [C.c_char_p, _P(sfmx_cloud_stats)]),
+    "sfmx_cloud_write_neighbors_csv": (C.c_int, [C.c_char_p, _vp, _vp, C.c_int64]),
+    "sfmx_cloud_write_quality_ply": (C.c_int, [C.c_char_p, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_double]),
     "sfmx_undistort_images": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "sfmx_sift_default_params": (None, [_vp]),
     "sfmx_sift_detect_compute": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int32, C.c_int32, _vp, _vp,

@@ -18,6 +18,9 @@ driver around them.  Stages after the match graph that sfmx does not accelerate
 (incremental registration / triangulation, MVS densify, mesh; SURVEY.md §8 marks
 them out of scope) are reported and skipped; ``--sfmx-plan`` (an sfmx-only flag)
 prints the resolved plan and stops before any device work.
+
+``Photogrammetrie -Prun=pcl-stats -Pinput=cloud.ply -Pstats=... -Pneighbors=... -Pquality=...`` is the
+second sub-program (PclStatsCli.cpp): the neighbour search of sfmx.cloud on the GPU, then the three files.
 """
 from __future__ import annotations
 
@@ -376,6 +379,46 @@ class PhotogrammetrieCli:
                         matches[off[p]:off[p + 1]])
 
 
+class PclStatsCli:
+    """PclStatsCli::main (cli/PclStatsCli.cpp:30-65): neighbour statistics of a PLY cloud or mesh.  The
+    nearest-neighbour search runs once on the GPU and feeds all three outputs (the reference builds a
+    k-d tree and searches once per output).  An input that cannot be read ends the run with an error
+    and exit code 255; the reference ignores loadPLYFile's result and goes on with an empty cloud."""
+    logger = AppLogger("PclStatsCli")
+
+    def __init__(self, args: AppArgs, exec_name: str = "Photogrammetrie"):
+        self.args = args
+        self.exec_name = exec_name
+
+    def main(self) -> int:
+        args, log = self.args, self.logger
+        if args.isFlag("help"):
+            log.log("help\n" + usage(self.exec_name, 2), LOG_INFO, True)
+            return EXIT_USAGE
+        from . import cloud
+        ply_input = args.getArg("input", "pointcloud.ply")
+        log.info("loading point cloud")
+        try:
+            ply = cloud.read_ply(ply_input)
+        except ValueError as e:
+            log.error(f"-Pinput={ply_input}: {e}")
+            return EXIT_USAGE
+        xyz = ply["xyz"]
+        outputs = [args.getArg(k, "") for k in ("stats", "neighbors", "quality")]
+        # the reference's `size > 1` guard: a cloud of at most one point has an empty distance list
+        dist = cloud.neighbor_distances(xyz) if len(xyz) > 1 and any(outputs) else np.zeros(0)
+        if outputs[0]:
+            log.info("writing statistics")
+            cloud.write_stats_csv(outputs[0], cloud.statistics(dist, len(xyz)))
+        if outputs[1]:
+            log.info("writing neighbours")
+            cloud.write_neighbors_csv(outputs[1], *cloud.neighbor_histogram(dist, -1.0))
+        if outputs[2]:
+            log.info("writing quality")
+            cloud.write_quality_ply(outputs[2], xyz, dist, ply["face_sizes"], ply["face_indices"])
+        return 0
+
+
 class App:
     logger = AppLogger("App")
 
@@ -395,8 +438,11 @@ class App:
         if run == "photogrammetrie":
             rc = PhotogrammetrieCli(args, exec_name).main()
         elif run == "pcl-stats":
-            App.logger.error("-Prun=pcl-stats (point-cloud statistics) is outside the sfmx hot path")
-            return EXIT_USAGE
+            if args.isFlag("sfmx-plan"):   # the dry run prints the photogrammetrie plan; pcl-stats has none
+                App.logger.error("-Prun=pcl-stats has no plan to print: --sfmx-plan is outside the sfmx hot path of "
+                                 "this sub-program")
+                return EXIT_USAGE
+            rc = PclStatsCli(args, exec_name).main()
         else:
             App.logger.log("help\n" + usage(exec_name, 0), LOG_INFO, True)
             return EXIT_USAGE
