@@ -37,6 +37,7 @@
 
 #include "../../include/sfmx_cloud.h"
 #include "cloud_host.hpp"
+#include "device_call.hpp"
 #include "match_common.hpp"
 
 namespace sfmx {
@@ -553,18 +554,7 @@ void cloud_brute_emit_kernel(const float4* __restrict__ sorted, int64_t n, Plan*
 thread_local float g_last_ms = -1.f;
 thread_local int64_t g_last_evals = 0, g_last_brute = 0;
 
-// Per device, kept between calls (as triangulate.hip): the device check's result, one device block for the
-// call's scratch (regrown with headroom), pinned words for the counters, two timing events.
-struct Slot {
-    bool checked = false;
-    char* dev = nullptr;
-    size_t dev_cap = 0;
-    char* pin = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    std::mutex mu;   // one call per device at a time
-};
-Slot g_slot[64];
-size_t r256(size_t b) { return (std::max<size_t>(b, 1) + 255) & ~(size_t)255; }
+Slot g_slot[64];   // csrc/device_call.hpp
 
 int fail(int code, const std::string& msg) {
     set_last_error(msg.c_str());
@@ -576,8 +566,6 @@ int fail(int code, const std::string& msg) {
 
 using namespace sfmx;
 using namespace sfmx::cloud;
-
-#define CCHK(expr) do { if ((expr) != hipSuccess) { rc = SFMX_EDEVICE; goto done; } } while (0)
 
 extern "C" {
 
@@ -593,7 +581,8 @@ int sfmx_cloud_neighbor_distances(const float* xyz, int64_t n, int32_t max_equal
     if (n < 0) return fail(SFMX_EINVAL, "negative point count");
     if (n > 0 && (!xyz || !out_distance)) return fail(SFMX_EINVAL, "null argument");
     if (n > (int64_t)INT32_MAX - 64) return fail(SFMX_ECAPACITY, "more than 2^31 - 65 points in one call");
-    const hipStream_t st = (hipStream_t)stream;
+    DeviceCall F(stream, !inputs_on_device);
+    const hipStream_t st = F.st;
     const int64_t K = 2 + (int64_t)std::max<int32_t>(0, max_equal);
     const unsigned ke = (unsigned)std::min<int64_t>(K, n);
     if (n <= 1 && !inputs_on_device) {   // nothing to search, nothing launched
@@ -602,27 +591,16 @@ int sfmx_cloud_neighbor_distances(const float* xyz, int64_t n, int32_t max_equal
         g_last_evals = g_last_brute = 0;
         return SFMX_OK;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SFMX_EDEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev || device >= 64) return fail(SFMX_EINVAL, "device index out of range");
-    Slot* S = &g_slot[device];
-    std::unique_lock<std::mutex> lock(S->mu);
-    if (!S->checked) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return fail(SFMX_EDEVICE, "sfmx kernels are built for gfx950 only");
-        S->checked = true;
-    }
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(device);
+    const int orc = F.open(g_slot, device);
+    if (orc != SFMX_OK) return orc;
+    Slot* const S = F.S;
     int rc = SFMX_OK;
     {
         if (n <= 1) {   // device outputs of an empty or one-point cloud
             if (n == 1) {
-                CCHK(hipMemsetAsync(out_distance, 0, sizeof(double), st));
-                if (out_neighbor) CCHK(hipMemsetAsync(out_neighbor, 0xff, sizeof(int64_t), st));
-                CCHK(hipStreamSynchronize(st));
+                SFMX_HIP_CHK(hipMemsetAsync(out_distance, 0, sizeof(double), st));
+                if (out_neighbor) SFMX_HIP_CHK(hipMemsetAsync(out_neighbor, 0xff, sizeof(int64_t), st));
+                SFMX_HIP_CHK(hipStreamSynchronize(st));
             }
             g_last_ms = 0.f;
             g_last_evals = g_last_brute = 0;
@@ -635,53 +613,35 @@ int sfmx_cloud_neighbor_distances(const float* xyz, int64_t n, int32_t max_equal
             const int64_t cells_target = std::min<int64_t>(std::max<int64_t>(n, 64), (int64_t)1 << 23), cells_limit = 16 * cells_target;
             const int64_t m_scan = cells_limit + 2;   // counts of the grid cells, the non-finite bucket, the end
             const int64_t nb_scan = (m_scan + SCAN_TILE - 1) / SCAN_TILE;
-            const size_t b_plan = r256(sizeof(Plan)), b_cnt = r256(sizeof(unsigned) * m_scan), b_bs = r256(sizeof(unsigned) * nb_scan),
-                         b_cell = r256(sizeof(int) * n), b_rank = r256(sizeof(unsigned) * n), b_sort = r256(sizeof(float4) * n), b_key = r256(sizeof(unsigned long long) * n),
-                         b_xyz = H ? r256(sizeof(float) * 3 * n) : 0, b_od = H ? r256(sizeof(double) * n) : 0,
-                         b_on = H && out_neighbor ? r256(sizeof(int64_t) * n) : 0;
-            const size_t need = b_plan + b_cnt + b_bs + b_cell + b_rank + b_sort + b_key + b_xyz + b_od + b_on;
-            if (S->dev_cap < need) {
-                if (S->dev) (void)hipFree(S->dev);
-                S->dev = nullptr;
-                S->dev_cap = 0;
-                if (hipMalloc(reinterpret_cast<void**>(&S->dev), need + need / 4) != hipSuccess) {
-                    S->dev = nullptr;
-                    (void)hipGetLastError();
-                    rc = SFMX_ENOMEM;
-                    goto done;
-                }
-                S->dev_cap = need + need / 4;
-            }
-            if (!S->pin && hipHostMalloc(reinterpret_cast<void**>(&S->pin), 256, hipHostMallocDefault) != hipSuccess) {
-                S->pin = nullptr;
-                rc = SFMX_ENOMEM;
-                goto done;
-            }
-            if (!S->e0 && (hipEventCreate(&S->e0) != hipSuccess || hipEventCreate(&S->e1) != hipSuccess)) { rc = SFMX_EDEVICE; goto done; }
-            char* d = S->dev;
-            Plan* plan = reinterpret_cast<Plan*>(d);                 d += b_plan;
-            unsigned* cnt = reinterpret_cast<unsigned*>(d);          d += b_cnt;
-            unsigned* bsum = reinterpret_cast<unsigned*>(d);         d += b_bs;
-            int* cell = reinterpret_cast<int*>(d);                   d += b_cell;   // after the scatter: the brute-force list
-            unsigned* rank = reinterpret_cast<unsigned*>(d);         d += b_rank;   // after the scatter: z of the brute-force queries
-            float4* sorted = reinterpret_cast<float4*>(d);           d += b_sort;
-            unsigned long long* bkey = reinterpret_cast<unsigned long long*>(d); d += b_key;
-            float* xd = reinterpret_cast<float*>(d);                 d += b_xyz;
-            double* odd = reinterpret_cast<double*>(d);              d += b_od;
-            int64_t* ond = reinterpret_cast<int64_t*>(d);
-            const float* px = xyz;
-            double* pod = out_distance;
-            int64_t* pon = out_neighbor;
-            if (H) {
-                CCHK(hipMemcpyAsync(xd, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, st));
-                px = xd;
-                pod = odd;
-                pon = out_neighbor ? ond : nullptr;
-            }
+            BlockLayout L;
+            Plan* plan;
+            unsigned *cnt, *bsum, *rank;
+            int* cell;
+            float4* sorted;
+            unsigned long long* bkey;
+            float* xd;
+            double* odd;
+            int64_t* ond;
+            L.want(plan, 1);
+            L.want(cnt, m_scan);
+            L.want(bsum, nb_scan);
+            L.want(cell, n);     // after the scatter: the brute-force list
+            L.want(rank, n);     // after the scatter: z of the brute-force queries
+            L.want(sorted, n);
+            L.want(bkey, n);
+            L.want(xd, 3 * n, H);
+            L.want(odd, n, H);
+            L.want(ond, n, H && out_neighbor);
+            rc = F.reserve(L, 256);   // pinned words for the counters
+            if (rc != SFMX_OK) goto done;
+            const float* px = F.in(xyz, xd, 3 * n);
+            SFMX_HIP_CHK(F.err);
+            double* pod = F.out(out_distance, odd);
+            int64_t* pon = F.out(out_neighbor, ond);
             const unsigned blocks = (unsigned)((n + BLOCK - 1) / BLOCK), stride_blocks = std::min<unsigned>(blocks, 2048u);
             (void)hipEventRecord(S->e0, st);
-            CCHK(hipMemsetAsync(plan, 0, sizeof(Plan), st));
-            CCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned) * m_scan, st));
+            SFMX_HIP_CHK(hipMemsetAsync(plan, 0, sizeof(Plan), st));
+            SFMX_HIP_CHK(hipMemsetAsync(cnt, 0, sizeof(unsigned) * m_scan, st));
             cloud_minmax_kernel<<<std::min<unsigned>(blocks, 1024u), BLOCK, 0, st>>>(px, n, plan);
             cloud_pick_kernel<<<1, BINS, 0, st>>>(plan, 0, cells_target);
             for (int round = 1; round <= ROUNDS; ++round) {
@@ -702,13 +662,11 @@ int sfmx_cloud_neighbor_distances(const float* xyz, int64_t n, int32_t max_equal
             cloud_brute_kernel<<<2048, BLOCK, 0, st>>>(sorted, n, plan, brute, bkey, rank);
             cloud_brute_emit_kernel<<<std::min<unsigned>(blocks, 1024u), BLOCK, 0, st>>>(sorted, n, plan, ke, brute, bkey, rank, pod, pon);
             (void)hipEventRecord(S->e1, st);
-            CCHK(hipGetLastError());
-            CCHK(hipMemcpyAsync(S->pin, plan, offsetof(Plan, lo), hipMemcpyDeviceToHost, st));
-            if (H) {
-                CCHK(hipMemcpyAsync(out_distance, odd, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-                if (out_neighbor) CCHK(hipMemcpyAsync(out_neighbor, ond, sizeof(int64_t) * n, hipMemcpyDeviceToHost, st));
-            }
-            CCHK(hipStreamSynchronize(st));
+            SFMX_HIP_CHK(hipGetLastError());
+            SFMX_HIP_CHK(hipMemcpyAsync(S->pin, plan, offsetof(Plan, lo), hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(F.back(out_distance, odd, n));
+            if (out_neighbor) SFMX_HIP_CHK(F.back(out_neighbor, ond, n));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
             const Plan* hp = reinterpret_cast<const Plan*>(S->pin);   // only the words before `lo` were copied
             if (hp->error || (int64_t)hp->n_brute > n || (int64_t)hp->n_finite > n) {
                 set_last_error("cloud grid self check failed");
@@ -722,11 +680,8 @@ int sfmx_cloud_neighbor_distances(const float* xyz, int64_t n, int32_t max_equal
             g_last_brute = (int64_t)hp->n_brute;
         }
     done:;
-        if (rc != SFMX_OK) (void)hipStreamSynchronize(st);
+        rc = F.finish(rc, "sfmx_cloud_neighbor_distances");
     }
-    if (rc == SFMX_EDEVICE) set_last_error("HIP error in sfmx_cloud_neighbor_distances");
-    if (rc == SFMX_ENOMEM) set_last_error("device allocation failed");
-    if (prev >= 0) (void)hipSetDevice(prev);
     return rc;
 }
 

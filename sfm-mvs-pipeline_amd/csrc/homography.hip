@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/sfmx_homography.h"
+#include "device_call.hpp"
 #include "diag.hpp"
 #include "match_common.hpp"
 
@@ -513,21 +514,10 @@ void homography_ransac_kernel(const float2* const* __restrict__ kp, const int32_
 
 thread_local float g_last_ms = -1.f;
 
-// Per device, kept between calls (r05): the device check's result, one device block for the call's
-// tables / outputs / scratch (regrown with headroom), pinned staging for the small uploads and the
-// ratios, two timing events.  r04 made ~7 hipMalloc / hipFree pairs, a device-properties query, a D2H
-// of the pair offsets and pageable copies per call: twice the kernel's time around a 0.3 ms kernel.
-struct Slot {
-    bool checked = false;
-    char* dev = nullptr;
-    size_t dev_cap = 0;
-    char* pin = nullptr;
-    size_t pin_cap = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    std::mutex mu;   // one call per device at a time; calls on different devices run concurrently
-};
+// The slot kept between calls (csrc/device_call.hpp) dates from r05.  r04 made ~7 hipMalloc / hipFree pairs, a
+// device-properties query, a D2H of the pair offsets and pageable copies per call: twice the kernel's time around
+// a 0.3 ms kernel.
 Slot g_slot[64];
-size_t r256(size_t b) { return (std::max<size_t>(b, 1) + 255) & ~(size_t)255; }
 
 }  // namespace homog
 }  // namespace sfmx
@@ -551,20 +541,10 @@ int sfmx_homography_ratios(const sfmx_point2f* const* keypoints, const int32_t* 
         return SFMX_EINVAL;
     }
     if (!(confidence > 0.0 && confidence < 1.0)) { set_last_error("confidence must be in (0, 1)"); return SFMX_EINVAL; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_last_error("no HIP device visible"); return SFMX_EDEVICE; }
-    if (device < 0 || device >= ndev) { set_last_error("device index out of range"); return SFMX_EINVAL; }
-    if (device >= 64) { set_last_error("device index out of range"); return SFMX_EINVAL; }
-    Slot& S = g_slot[device];
-    std::lock_guard<std::mutex> lock(S.mu);
-    if (!S.checked) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-            set_last_error("sfmx kernels are built for gfx950 only");
-            return SFMX_EDEVICE;
-        }
-        S.checked = true;
-    }
+    DeviceCall F(stream, !inputs_on_device);
+    const int orc = F.open(g_slot, device);
+    if (orc != SFMX_OK) return orc;
+    Slot& S = *F.S;
     std::vector<PairH> ph(n_pairs);
     int64_t bound = 0;   // device inputs: the scratch bound (at most one match per query keypoint)
     for (int p = 0; p < n_pairs; ++p) {
@@ -576,10 +556,7 @@ int sfmx_homography_ratios(const sfmx_point2f* const* keypoints, const int32_t* 
         ph[p] = PairH{L, R, thr};
         bound += std::max(n_keypoints[L], 0);
     }
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(device);
-    const hipStream_t st = (hipStream_t)stream;
+    const hipStream_t st = F.st;
     int rc = SFMX_OK;
     {
         int64_t total = bound, nk = 0;
@@ -601,95 +578,61 @@ int sfmx_homography_ratios(const sfmx_point2f* const* keypoints, const int32_t* 
         {
             // device block: [keypoint table | counts | pairs | ratios | scratch | (host inputs: keypoints,
             // matches, offsets)]; the first three parts staged back to back and copied up at once
-            const size_t b_kp = r256(sizeof(float2*) * std::max(n_imgs, 1)), b_nk = r256(sizeof(int32_t) * std::max(n_imgs, 1)),
-                         b_ph = r256(sizeof(PairH) * n_pairs), b_out = r256(sizeof(double) * n_pairs),
-                         b_scr = r256(sizeof(float4) * std::max<int64_t>(total, 1));
-            const size_t b_kd = inputs_on_device ? 0 : r256(sizeof(float2) * nk),
-                         b_md = inputs_on_device ? 0 : r256(sizeof(sfmx_dmatch) * total),
-                         b_od = inputs_on_device ? 0 : r256(sizeof(int64_t) * (n_pairs + 1));
-            const size_t need = b_kp + b_nk + b_ph + b_out + b_scr + b_kd + b_md + b_od;
-            if (S.dev_cap < need) {
-                if (S.dev) (void)hipFree(S.dev);
-                S.dev = nullptr;
-                S.dev_cap = 0;
-                if (hipMalloc(reinterpret_cast<void**>(&S.dev), need + need / 4) != hipSuccess) {
-                    S.dev = nullptr;
-                    (void)hipGetLastError();
-                    rc = SFMX_ENOMEM;
-                    goto done;
-                }
-                S.dev_cap = need + need / 4;
-            }
-            const size_t need_pin = b_kp + b_nk + b_ph + b_out;
-            if (S.pin_cap < need_pin) {
-                if (S.pin) (void)hipHostFree(S.pin);
-                S.pin = nullptr;
-                S.pin_cap = 0;
-                if (hipHostMalloc(reinterpret_cast<void**>(&S.pin), need_pin + need_pin / 4, hipHostMallocDefault) != hipSuccess) {
-                    S.pin = nullptr;
-                    rc = SFMX_ENOMEM;
-                    goto done;
-                }
-                S.pin_cap = need_pin + need_pin / 4;
-            }
-            if (!S.e0 && (hipEventCreate(&S.e0) != hipSuccess || hipEventCreate(&S.e1) != hipSuccess)) { rc = SFMX_EDEVICE; goto done; }
-            char* d = S.dev;
-            const float2** kpd = reinterpret_cast<const float2**>(d);
-            int32_t* nkd = reinterpret_cast<int32_t*>(d + b_kp);
-            PairH* phd = reinterpret_cast<PairH*>(d + b_kp + b_nk);
-            double* outd = reinterpret_cast<double*>(d + b_kp + b_nk + b_ph);
-            float4* scr = reinterpret_cast<float4*>(d + b_kp + b_nk + b_ph + b_out);
-            char* hx = d + b_kp + b_nk + b_ph + b_out + b_scr;
-            const float2** hk = reinterpret_cast<const float2**>(S.pin);
-            const int64_t* doff = pair_offsets;
+            BlockLayout L;
+            const float2** kpd;
+            int32_t* nkd;
+            PairH* phd;
+            double* outd;
+            float4* scr;
+            float2* kd;
+            sfmx_dmatch* md;
+            int64_t* od;
+            L.want(kpd, std::max(n_imgs, 1));
+            L.want(nkd, std::max(n_imgs, 1));
+            L.want(phd, n_pairs);
+            const size_t b_tab = L.need;
+            L.want(outd, n_pairs);
+            const size_t need_pin = L.need;   // the ratios come back through pinned memory
+            L.want(scr, std::max<int64_t>(total, 1));
+            L.want(kd, nk, F.host);
+            L.want(md, total, F.host);
+            L.want(od, n_pairs + 1, F.host);
+            rc = F.reserve(L, need_pin);
+            if (rc != SFMX_OK) goto done;
+            const float2** hk = F.pinned(kpd);
             if (inputs_on_device) {
                 for (int i = 0; i < n_imgs; ++i) hk[i] = reinterpret_cast<const float2*>(keypoints[i]);
             } else {   // host inputs: keypoints, matches and offsets go up (pageable copies)
-                float2* kd = reinterpret_cast<float2*>(hx);
-                auto* md = reinterpret_cast<sfmx_dmatch*>(hx + b_kd);
-                auto* od = reinterpret_cast<int64_t*>(hx + b_kd + b_md);
                 int64_t o = 0;
                 for (int i = 0; i < n_imgs; ++i) {
-                    if (n_keypoints[i] &&
-                        hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st) != hipSuccess) {
-                        rc = SFMX_EDEVICE; goto done;
-                    }
+                    if (n_keypoints[i]) SFMX_HIP_CHK(hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st));
                     hk[i] = kd + o;
                     o += n_keypoints[i];
                 }
-                if ((total && hipMemcpyAsync(md, matches, sizeof(sfmx_dmatch) * total, hipMemcpyHostToDevice, st) != hipSuccess) ||
-                    hipMemcpyAsync(od, pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyHostToDevice, st) != hipSuccess) {
-                    rc = SFMX_EDEVICE; goto done;
-                }
-                matches = md;
-                doff = od;
             }
-            std::memcpy(S.pin + b_kp, n_keypoints, sizeof(int32_t) * n_imgs);
-            std::memcpy(S.pin + b_kp + b_nk, ph.data(), sizeof(PairH) * n_pairs);
-            double* hout = reinterpret_cast<double*>(S.pin + b_kp + b_nk + b_ph);
-            if (hipMemcpyAsync(d, S.pin, b_kp + b_nk + b_ph, hipMemcpyHostToDevice, st) != hipSuccess) { rc = SFMX_EDEVICE; goto done; }
+            if (total) matches = F.in(matches, md, total);
+            const int64_t* doff = F.in(pair_offsets, od, n_pairs + 1);
+            SFMX_HIP_CHK(F.err);
+            std::memcpy(F.pinned(nkd), n_keypoints, sizeof(int32_t) * n_imgs);
+            std::memcpy(F.pinned(phd), ph.data(), sizeof(PairH) * n_pairs);
+            double* hout = F.pinned(outd);
+            SFMX_HIP_CHK(F.upload(b_tab));
             (void)hipEventRecord(S.e0, st);
             homography_ransac_kernel<<<n_pairs, 256, 0, st>>>(kpd, nkd, phd, reinterpret_cast<const DMatchDev*>(matches),
                                                               doff, scr, std::max<int64_t>(total, 1), max_iters, confidence, outd,
                                                               SFMX_DIAG_ENV("SFMX_HOMOG_SERIAL") ? 1 : 0);
             (void)hipEventRecord(S.e1, st);
-            if (hipGetLastError() != hipSuccess ||
-                hipMemcpyAsync(hout, outd, sizeof(double) * n_pairs, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) {
-                rc = SFMX_EDEVICE;
-            } else {
-                std::memcpy(out_ratio, hout, sizeof(double) * n_pairs);
-                float ms = -1.f;
-                (void)hipEventElapsedTime(&ms, S.e0, S.e1);
-                g_last_ms = ms;
-            }
+            SFMX_HIP_CHK(hipGetLastError());
+            SFMX_HIP_CHK(hipMemcpyAsync(hout, outd, sizeof(double) * n_pairs, hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
+            std::memcpy(out_ratio, hout, sizeof(double) * n_pairs);
+            float ms = -1.f;
+            (void)hipEventElapsedTime(&ms, S.e0, S.e1);
+            g_last_ms = ms;
         }
     done:;
-        if (rc != SFMX_OK) (void)hipStreamSynchronize(st);   // nothing in flight from the pinned staging
+        rc = F.finish(rc, "sfmx_homography_ratios");
     }
-    if (rc == SFMX_EDEVICE) set_last_error("HIP error in sfmx_homography_ratios");
-    if (rc == SFMX_ENOMEM) set_last_error("device allocation failed");
-    if (prev >= 0) (void)hipSetDevice(prev);
     return rc;
 }
 

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../../include/sfmx_pnp.h"
+#include "device_call.hpp"
 #include "match_common.hpp"
 #include "pnp_math.hpp"
 
@@ -524,71 +525,13 @@ void distinct_write_kernel(const double* __restrict__ c5, const uint8_t* __restr
 thread_local float g_last_ms = -1.f;
 thread_local float g_distinct_ms = -1.f;
 
-// Per device, kept between calls (as pose.hip): the device check's result, one device block for the call's
-// tables and scratch (regrown with headroom), pinned staging for the small uploads, two timing events.
-struct Slot {
-    bool checked = false;
-    char* dev = nullptr;
-    size_t dev_cap = 0;
-    char* pin = nullptr;
-    size_t pin_cap = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    std::mutex mu;   // one call per device at a time
-};
-Slot g_slot[64];
-size_t r256(size_t b) { return (std::max<size_t>(b, 1) + 255) & ~(size_t)255; }
-
-// the slot of `device`, checked for gfx950; SFMX_OK or the error code
-int open_slot(int device, Slot** out) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_last_error("no HIP device visible"); return SFMX_EDEVICE; }
-    if (device < 0 || device >= ndev || device >= 64) { set_last_error("device index out of range"); return SFMX_EINVAL; }
-    *out = &g_slot[device];
-    return SFMX_OK;
-}
-int check_arch(Slot* S, int device) {
-    if (S->checked) return SFMX_OK;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_last_error("sfmx kernels are built for gfx950 only");
-        return SFMX_EDEVICE;
-    }
-    S->checked = true;
-    return SFMX_OK;
-}
-int reserve(Slot* S, size_t need, size_t need_pin) {
-    if (S->dev_cap < need) {
-        if (S->dev) (void)hipFree(S->dev);
-        S->dev = nullptr;
-        S->dev_cap = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&S->dev), need + need / 4) != hipSuccess) {
-            S->dev = nullptr;
-            (void)hipGetLastError();
-            return SFMX_ENOMEM;
-        }
-        S->dev_cap = need + need / 4;
-    }
-    if (S->pin_cap < need_pin) {
-        if (S->pin) (void)hipHostFree(S->pin);
-        S->pin = nullptr;
-        S->pin_cap = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&S->pin), need_pin + need_pin / 4, hipHostMallocDefault) != hipSuccess) {
-            S->pin = nullptr;
-            return SFMX_ENOMEM;
-        }
-        S->pin_cap = need_pin + need_pin / 4;
-    }
-    if (!S->e0 && (hipEventCreate(&S->e0) != hipSuccess || hipEventCreate(&S->e1) != hipSuccess)) return SFMX_EDEVICE;
-    return SFMX_OK;
-}
+Slot g_slot[64];   // csrc/device_call.hpp
 
 }  // namespace pnp
 }  // namespace sfmx
 
 using namespace sfmx;
 using namespace sfmx::pnp;
-
-#define PCHK(expr) do { if ((expr) != hipSuccess) { rc = SFMX_EDEVICE; goto done; } } while (0)
 
 extern "C" {
 
@@ -616,29 +559,21 @@ int sfmx_register_poses(const double* points3d, const double* points2d, const in
         if (shot_camera[s] < 0 || shot_camera[s] >= n_cameras) { set_last_error("shot camera index out of range"); return SFMX_EINVAL; }
     for (int s = 0; s < n_sets; ++s)
         if (set_shot[s] < 0 || set_shot[s] >= n_shots) { set_last_error("set shot index out of range"); return SFMX_EINVAL; }
-    const hipStream_t st = (hipStream_t)stream;
-    Slot* S = nullptr;
-    int prev = -1;
+    DeviceCall F(stream, !inputs_on_device);
+    const hipStream_t st = F.st;
     if (inputs_on_device ? n_sets > 0 : set_offsets[n_sets] != 0) {   // anything but an empty call needs the device
-        const int orc = open_slot(device, &S);
+        const int orc = F.open(g_slot, device);
         if (orc != SFMX_OK) return orc;
     }
-    std::unique_lock<std::mutex> lock;
-    if (S) {
-        lock = std::unique_lock<std::mutex>(S->mu);
-        const int arc = check_arch(S, device);
-        if (arc != SFMX_OK) return arc;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(device);
-    }
+    Slot* const S = F.S;
     int rc = SFMX_OK;
     {
         std::vector<int64_t> hoff(n_sets + 1);
         std::vector<double> nanv;
         int64_t n = 0, longest = 0;
         if (inputs_on_device && n_sets > 0) {
-            PCHK(hipMemcpyAsync(hoff.data(), set_offsets, sizeof(int64_t) * (n_sets + 1), hipMemcpyDeviceToHost, st));
-            PCHK(hipStreamSynchronize(st));
+            SFMX_HIP_CHK(hipMemcpyAsync(hoff.data(), set_offsets, sizeof(int64_t) * (n_sets + 1), hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
         } else if (!inputs_on_device) {
             std::memcpy(hoff.data(), set_offsets, sizeof(int64_t) * (n_sets + 1));
         } else {
@@ -658,13 +593,13 @@ int sfmx_register_poses(const double* points3d, const double* points2d, const in
             std::vector<double> neg((size_t)n_sets, -1.0);
             std::vector<int32_t> negi((size_t)n_sets, -1);
             if (inputs_on_device && n_sets) {
-                PCHK(hipMemsetAsync(out_status, 0, sizeof(int32_t) * n_sets, st));
-                PCHK(hipMemsetAsync(out_n_inliers, 0, sizeof(int32_t) * n_sets, st));
-                PCHK(hipMemcpyAsync(out_ransac_pose, nanv.data(), sizeof(double) * 12 * n_sets, hipMemcpyHostToDevice, st));
-                PCHK(hipMemcpyAsync(out_pose, nanv.data(), sizeof(double) * 12 * n_sets, hipMemcpyHostToDevice, st));
-                PCHK(hipMemcpyAsync(out_refit_start, negi.data(), sizeof(int32_t) * n_sets, hipMemcpyHostToDevice, st));
-                PCHK(hipMemcpyAsync(out_inlier_ratio, neg.data(), sizeof(double) * n_sets, hipMemcpyHostToDevice, st));
-                PCHK(hipStreamSynchronize(st));
+                SFMX_HIP_CHK(hipMemsetAsync(out_status, 0, sizeof(int32_t) * n_sets, st));
+                SFMX_HIP_CHK(hipMemsetAsync(out_n_inliers, 0, sizeof(int32_t) * n_sets, st));
+                SFMX_HIP_CHK(hipMemcpyAsync(out_ransac_pose, nanv.data(), sizeof(double) * 12 * n_sets, hipMemcpyHostToDevice, st));
+                SFMX_HIP_CHK(hipMemcpyAsync(out_pose, nanv.data(), sizeof(double) * 12 * n_sets, hipMemcpyHostToDevice, st));
+                SFMX_HIP_CHK(hipMemcpyAsync(out_refit_start, negi.data(), sizeof(int32_t) * n_sets, hipMemcpyHostToDevice, st));
+                SFMX_HIP_CHK(hipMemcpyAsync(out_inlier_ratio, neg.data(), sizeof(double) * n_sets, hipMemcpyHostToDevice, st));
+                SFMX_HIP_CHK(hipStreamSynchronize(st));
             } else if (n_sets) {
                 std::memset(out_status, 0, sizeof(int32_t) * n_sets);
                 std::memset(out_n_inliers, 0, sizeof(int32_t) * n_sets);
@@ -679,28 +614,27 @@ int sfmx_register_poses(const double* points3d, const double* points2d, const in
         if (!points3d || !points2d || !out_mask) { set_last_error("null argument"); rc = SFMX_EINVAL; goto done; }
         {
             // device block: [set table | (host inputs: points, offsets, every output)]
-            const bool H = !inputs_on_device;
-            const size_t b_st = r256(sizeof(SetP) * n_sets);
-            const size_t b_p3 = H ? r256(sizeof(double) * 3 * n) : 0, b_p2 = H ? r256(sizeof(double) * 2 * n) : 0,
-                         b_od = H ? r256(sizeof(int64_t) * (n_sets + 1)) : 0, b_os = H ? r256(sizeof(int32_t) * n_sets) : 0,
-                         b_op = H ? r256(sizeof(double) * 12 * n_sets) : 0, b_ok = H ? r256((size_t)n) : 0,
-                         b_oi = H ? r256(sizeof(int32_t) * n_sets) : 0, b_or = H ? r256(sizeof(double) * n_sets) : 0,
-                         b_of = H ? r256(sizeof(double) * 12 * n_sets) : 0, b_ob = H ? r256(sizeof(int32_t) * n_sets) : 0;
-            rc = reserve(S, b_st + b_p3 + b_p2 + b_od + b_os + b_op + b_ok + b_oi + b_or + b_of + b_ob, b_st);
+            const size_t ns = (size_t)n_sets;
+            BlockLayout L;
+            SetP* std_;
+            double *p3d, *p2d, *opd, *ord_, *ofd;
+            int64_t* od;
+            int32_t *osd, *oid, *obd;
+            uint8_t* okd;
+            L.want(std_, n_sets);
+            L.want(p3d, 3 * n, F.host);
+            L.want(p2d, 2 * n, F.host);
+            L.want(od, n_sets + 1, F.host);
+            L.want(osd, n_sets, F.host);
+            L.want(opd, 12 * ns, F.host);
+            L.want(okd, n, F.host);
+            L.want(oid, n_sets, F.host);
+            L.want(ord_, n_sets, F.host);
+            L.want(ofd, 12 * ns, F.host);
+            L.want(obd, n_sets, F.host);
+            rc = F.reserve(L, r256(sizeof(SetP) * n_sets));
             if (rc != SFMX_OK) goto done;
-            char* d = S->dev;
-            SetP* std_ = reinterpret_cast<SetP*>(d);                 d += b_st;
-            double* p3d = reinterpret_cast<double*>(d);              d += b_p3;
-            double* p2d = reinterpret_cast<double*>(d);              d += b_p2;
-            int64_t* od = reinterpret_cast<int64_t*>(d);             d += b_od;
-            int32_t* osd = reinterpret_cast<int32_t*>(d);            d += b_os;
-            double* opd = reinterpret_cast<double*>(d);              d += b_op;
-            uint8_t* okd = reinterpret_cast<uint8_t*>(d);            d += b_ok;
-            int32_t* oid = reinterpret_cast<int32_t*>(d);            d += b_oi;
-            double* ord_ = reinterpret_cast<double*>(d);             d += b_or;
-            double* ofd = reinterpret_cast<double*>(d);              d += b_of;
-            int32_t* obd = reinterpret_cast<int32_t*>(d);
-            SetP* hs = reinterpret_cast<SetP*>(S->pin);
+            SetP* hs = F.pinned(std_);
             for (int s = 0; s < n_sets; ++s) {
                 const int sh = set_shot[s];
                 const sfmx_tri_camera& c = cameras[shot_camera[sh]];
@@ -711,44 +645,33 @@ int sfmx_register_poses(const double* points3d, const double* points2d, const in
                 hs[s].thr2 = (float)(tf * tf);
                 hs[s]._pad = 0;
             }
-            PCHK(hipMemcpyAsync(std_, S->pin, sizeof(SetP) * n_sets, hipMemcpyHostToDevice, st));
-            const double *d3 = points3d, *d2 = points2d;
-            const int64_t* doff = set_offsets;
-            int32_t *dst = out_status, *dni = out_n_inliers;
-            double *dP = out_ransac_pose, *dr = out_inlier_ratio, *dF = out_pose;
-            int32_t* dB = out_refit_start;
-            uint8_t* dk = out_mask;
-            if (H) {
-                PCHK(hipMemcpyAsync(p3d, points3d, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
-                PCHK(hipMemcpyAsync(p2d, points2d, sizeof(double) * 2 * n, hipMemcpyHostToDevice, st));
-                PCHK(hipMemcpyAsync(od, set_offsets, sizeof(int64_t) * (n_sets + 1), hipMemcpyHostToDevice, st));
-                d3 = p3d; d2 = p2d; doff = od; dst = osd; dni = oid; dP = opd; dr = ord_; dk = okd; dF = ofd; dB = obd;
-            }
+            SFMX_HIP_CHK(F.upload(sizeof(SetP) * n_sets));
+            const double *d3 = F.in(points3d, p3d, 3 * n), *d2 = F.in(points2d, p2d, 2 * n);
+            const int64_t* doff = F.in(set_offsets, od, n_sets + 1);
+            SFMX_HIP_CHK(F.err);
+            int32_t *dst = F.out(out_status, osd), *dni = F.out(out_n_inliers, oid), *dB = F.out(out_refit_start, obd);
+            double *dP = F.out(out_ransac_pose, opd), *dr = F.out(out_inlier_ratio, ord_), *dF = F.out(out_pose, ofd);
+            uint8_t* dk = F.out(out_mask, okd);
             (void)hipEventRecord(S->e0, st);
             pnp_set_kernel<<<(unsigned)n_sets, BLOCK, 0, st>>>(std_, d3, d2, doff, max_iters, confidence, dst, dP, dk, dni, dr);
             pnp_refit_kernel<<<(unsigned)n_sets, BLOCK, 0, st>>>(std_, d3, d2, doff, dst, dP, dk, dni, dr, dF, dB);
             (void)hipEventRecord(S->e1, st);
-            PCHK(hipGetLastError());
-            if (H) {
-                PCHK(hipMemcpyAsync(out_status, osd, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_ransac_pose, opd, sizeof(double) * 12 * n_sets, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_mask, okd, (size_t)n, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_n_inliers, oid, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_inlier_ratio, ord_, sizeof(double) * n_sets, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_pose, ofd, sizeof(double) * 12 * n_sets, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_refit_start, obd, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, st));
-            }
-            PCHK(hipStreamSynchronize(st));   // the pinned set table is reused by the next call
+            SFMX_HIP_CHK(hipGetLastError());
+            SFMX_HIP_CHK(F.back(out_status, osd, n_sets));
+            SFMX_HIP_CHK(F.back(out_ransac_pose, opd, 12 * ns));
+            SFMX_HIP_CHK(F.back(out_mask, okd, n));
+            SFMX_HIP_CHK(F.back(out_n_inliers, oid, n_sets));
+            SFMX_HIP_CHK(F.back(out_inlier_ratio, ord_, n_sets));
+            SFMX_HIP_CHK(F.back(out_pose, ofd, 12 * ns));
+            SFMX_HIP_CHK(F.back(out_refit_start, obd, n_sets));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));   // the pinned set table is reused by the next call
             float ms = -1.f;
             (void)hipEventElapsedTime(&ms, S->e0, S->e1);
             g_last_ms = ms;
         }
     done:;
-        if (rc != SFMX_OK && S) (void)hipStreamSynchronize(st);   // nothing in flight from the pinned staging
+        rc = F.finish(rc, "sfmx_register_poses");
     }
-    if (rc == SFMX_EDEVICE) set_last_error("HIP error in sfmx_register_poses");
-    if (rc == SFMX_ENOMEM) set_last_error("device allocation failed");
-    if (prev >= 0) (void)hipSetDevice(prev);
     return rc;
 }
 
@@ -757,28 +680,20 @@ int sfmx_distinct_3d2d_points(const double* cloud_xyz, int32_t n_points, const i
                               int32_t device, void* stream, double* out_xyz, double* out_xy, int64_t* out_n) {
     if (n_points < 0) { set_last_error("negative count"); return SFMX_EINVAL; }
     if (!origin_offsets || !out_n) { set_last_error("null argument"); return SFMX_EINVAL; }
-    const hipStream_t st = (hipStream_t)stream;
-    Slot* S = nullptr;
-    int prev = -1;
+    DeviceCall F(stream, !inputs_on_device);
+    const hipStream_t st = F.st;
     if (inputs_on_device ? n_points > 0 : origin_offsets[n_points] != 0) {
-        const int orc = open_slot(device, &S);
+        const int orc = F.open(g_slot, device);
         if (orc != SFMX_OK) return orc;
     }
-    std::unique_lock<std::mutex> lock;
-    if (S) {
-        lock = std::unique_lock<std::mutex>(S->mu);
-        const int arc = check_arch(S, device);
-        if (arc != SFMX_OK) return arc;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(device);
-    }
+    Slot* const S = F.S;
     int rc = SFMX_OK;
     {
         std::vector<int64_t> hoff((size_t)n_points + 1);
         int64_t nr = 0;
         if (inputs_on_device && n_points > 0) {
-            PCHK(hipMemcpyAsync(hoff.data(), origin_offsets, sizeof(int64_t) * ((size_t)n_points + 1), hipMemcpyDeviceToHost, st));
-            PCHK(hipStreamSynchronize(st));
+            SFMX_HIP_CHK(hipMemcpyAsync(hoff.data(), origin_offsets, sizeof(int64_t) * ((size_t)n_points + 1), hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
         } else if (!inputs_on_device) {
             std::memcpy(hoff.data(), origin_offsets, sizeof(int64_t) * ((size_t)n_points + 1));
         } else {
@@ -794,39 +709,32 @@ int sfmx_distinct_3d2d_points(const double* cloud_xyz, int32_t n_points, const i
         {
             // device block: [record -> point | flags | positions | five doubles per matched record | keep | positions
             // | (host inputs: cloud, offsets, found_*, outputs)]
-            const bool H = !inputs_on_device;
-            const size_t b_rp = r256(sizeof(int32_t) * nr), b_fl = r256((size_t)nr), b_ps = r256(sizeof(int64_t) * (nr + 1)),
-                         b_c5 = r256(sizeof(double) * 5 * nr), b_kp = r256((size_t)nr), b_p2 = r256(sizeof(int64_t) * (nr + 1));
-            const size_t b_xyz = H ? r256(sizeof(double) * 3 * n_points) : 0, b_of = H ? r256(sizeof(int64_t) * ((size_t)n_points + 1)) : 0,
-                         b_fk = H ? r256(sizeof(int32_t) * nr) : 0, b_fx = H ? r256(sizeof(float) * 2 * nr) : 0,
-                         b_o3 = H ? r256(sizeof(double) * 3 * nr) : 0, b_o2 = H ? r256(sizeof(double) * 2 * nr) : 0;
-            rc = reserve(S, b_rp + b_fl + b_ps + b_c5 + b_kp + b_p2 + b_xyz + b_of + b_fk + b_fx + b_o3 + b_o2, 256);
+            BlockLayout L;
+            int32_t *rp, *fkd;
+            uint8_t *fl, *kp;
+            int64_t *ps, *ps2, *ofd;
+            double *c5, *xyzd, *o3d, *o2d;
+            float* fxd;
+            L.want(rp, nr);
+            L.want(fl, nr);
+            L.want(ps, nr + 1);
+            L.want(c5, 5 * nr);
+            L.want(kp, nr);
+            L.want(ps2, nr + 1);
+            L.want(xyzd, 3 * (size_t)n_points, F.host);
+            L.want(ofd, (size_t)n_points + 1, F.host);
+            L.want(fkd, nr, F.host);
+            L.want(fxd, 2 * nr, F.host);
+            L.want(o3d, 3 * nr, F.host);
+            L.want(o2d, 2 * nr, F.host);
+            rc = F.reserve(L, 256);
             if (rc != SFMX_OK) goto done;
-            char* d = S->dev;
-            int32_t* rp = reinterpret_cast<int32_t*>(d);     d += b_rp;
-            uint8_t* fl = reinterpret_cast<uint8_t*>(d);     d += b_fl;
-            int64_t* ps = reinterpret_cast<int64_t*>(d);     d += b_ps;
-            double* c5 = reinterpret_cast<double*>(d);       d += b_c5;
-            uint8_t* kp = reinterpret_cast<uint8_t*>(d);     d += b_kp;
-            int64_t* ps2 = reinterpret_cast<int64_t*>(d);    d += b_p2;
-            double* xyzd = reinterpret_cast<double*>(d);     d += b_xyz;
-            int64_t* ofd = reinterpret_cast<int64_t*>(d);    d += b_of;
-            int32_t* fkd = reinterpret_cast<int32_t*>(d);    d += b_fk;
-            float* fxd = reinterpret_cast<float*>(d);        d += b_fx;
-            double* o3d = reinterpret_cast<double*>(d);      d += b_o3;
-            double* o2d = reinterpret_cast<double*>(d);
-            const double* dxyz = cloud_xyz;
-            const int64_t* dof = origin_offsets;
-            const int32_t* dfk = found_keypoint;
-            const float* dfx = found_xy;
-            double *do3 = out_xyz, *do2 = out_xy;
-            if (H) {
-                PCHK(hipMemcpyAsync(xyzd, cloud_xyz, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice, st));
-                PCHK(hipMemcpyAsync(ofd, origin_offsets, sizeof(int64_t) * ((size_t)n_points + 1), hipMemcpyHostToDevice, st));
-                PCHK(hipMemcpyAsync(fkd, found_keypoint, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st));
-                PCHK(hipMemcpyAsync(fxd, found_xy, sizeof(float) * 2 * nr, hipMemcpyHostToDevice, st));
-                dxyz = xyzd; dof = ofd; dfk = fkd; dfx = fxd; do3 = o3d; do2 = o2d;
-            }
+            const double* dxyz = F.in(cloud_xyz, xyzd, 3 * (size_t)n_points);
+            const int64_t* dof = F.in(origin_offsets, ofd, (size_t)n_points + 1);
+            const int32_t* dfk = F.in(found_keypoint, fkd, nr);
+            const float* dfx = F.in(found_xy, fxd, 2 * nr);
+            SFMX_HIP_CHK(F.err);
+            double *do3 = F.out(out_xyz, o3d), *do2 = F.out(out_xy, o2d);
             const unsigned gp = (unsigned)((n_points + BLOCK - 1) / BLOCK), gr = (unsigned)((nr + BLOCK - 1) / BLOCK);
             (void)hipEventRecord(S->e0, st);
             distinct_mark_kernel<<<gp, BLOCK, 0, st>>>(dof, n_points, dfk, rp, fl);
@@ -836,16 +744,16 @@ int sfmx_distinct_3d2d_points(const double* cloud_xyz, int32_t n_points, const i
             distinct_scan_kernel<<<1, 1024, 0, st>>>(kp, nr, ps2);
             distinct_write_kernel<<<gr, BLOCK, 0, st>>>(c5, kp, ps2, nr, do3, do2);
             (void)hipEventRecord(S->e1, st);
-            PCHK(hipGetLastError());
+            SFMX_HIP_CHK(hipGetLastError());
             int64_t* htot = reinterpret_cast<int64_t*>(S->pin);
-            PCHK(hipMemcpyAsync(htot, ps2 + nr, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            PCHK(hipStreamSynchronize(st));
+            SFMX_HIP_CHK(hipMemcpyAsync(htot, ps2 + nr, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
             const int64_t total = *htot;
             if (total < 0 || total > nr) { set_last_error("distinct count self check failed"); rc = SFMX_EINTERNAL; goto done; }
-            if (H && total) {
-                PCHK(hipMemcpyAsync(out_xyz, o3d, sizeof(double) * 3 * total, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_xy, o2d, sizeof(double) * 2 * total, hipMemcpyDeviceToHost, st));
-                PCHK(hipStreamSynchronize(st));
+            if (F.host && total) {
+                SFMX_HIP_CHK(F.back(out_xyz, o3d, 3 * total));
+                SFMX_HIP_CHK(F.back(out_xy, o2d, 2 * total));
+                SFMX_HIP_CHK(hipStreamSynchronize(st));
             }
             *out_n = total;
             float ms = -1.f;
@@ -853,11 +761,8 @@ int sfmx_distinct_3d2d_points(const double* cloud_xyz, int32_t n_points, const i
             g_distinct_ms = ms;
         }
     done:;
-        if (rc != SFMX_OK && S) (void)hipStreamSynchronize(st);
+        rc = F.finish(rc, "sfmx_distinct_3d2d_points");
     }
-    if (rc == SFMX_EDEVICE) set_last_error("HIP error in sfmx_distinct_3d2d_points");
-    if (rc == SFMX_ENOMEM) set_last_error("device allocation failed");
-    if (prev >= 0) (void)hipSetDevice(prev);
     return rc;
 }
 

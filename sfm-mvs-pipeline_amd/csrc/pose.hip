@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/sfmx_pose.h"
+#include "device_call.hpp"
 #include "match_common.hpp"
 #include "pose_math.hpp"
 
@@ -337,28 +338,13 @@ void pose_compact_kernel(const DMatchDev* __restrict__ matches, const int64_t* _
 
 thread_local float g_last_ms = -1.f;
 
-// Per device, kept between calls (as triangulate.hip): the device check's result, one device block for the
-// call's tables and scratch (regrown with headroom), pinned staging for the small uploads and the result words,
-// two timing events.
-struct Slot {
-    bool checked = false;
-    char* dev = nullptr;
-    size_t dev_cap = 0;
-    char* pin = nullptr;
-    size_t pin_cap = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    std::mutex mu;   // one call per device at a time
-};
-Slot g_slot[64];
-size_t r256(size_t b) { return (std::max<size_t>(b, 1) + 255) & ~(size_t)255; }
+Slot g_slot[64];   // csrc/device_call.hpp
 
 }  // namespace pose
 }  // namespace sfmx
 
 using namespace sfmx;
 using namespace sfmx::pose;
-
-#define PCHK(expr) do { if ((expr) != hipSuccess) { rc = SFMX_EDEVICE; goto done; } } while (0)
 
 extern "C" {
 
@@ -392,29 +378,13 @@ int sfmx_relative_poses(const sfmx_point2f* const* keypoints, const int32_t* n_k
             set_last_error("pair shot index out of range");
             return SFMX_EINVAL;
         }
-    const hipStream_t st = (hipStream_t)stream;
-    Slot* S = nullptr;
-    int prev = -1;
+    DeviceCall F(stream, !inputs_on_device);
+    const hipStream_t st = F.st;
     if (inputs_on_device || pair_offsets[n_pairs] != 0) {   // anything but an empty host call needs the device
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_last_error("no HIP device visible"); return SFMX_EDEVICE; }
-        if (device < 0 || device >= ndev || device >= 64) { set_last_error("device index out of range"); return SFMX_EINVAL; }
-        S = &g_slot[device];
+        const int orc = F.open(g_slot, device);
+        if (orc != SFMX_OK) return orc;
     }
-    std::unique_lock<std::mutex> lock;
-    if (S) {
-        lock = std::unique_lock<std::mutex>(S->mu);
-        if (!S->checked) {
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-                set_last_error("sfmx kernels are built for gfx950 only");
-                return SFMX_EDEVICE;
-            }
-            S->checked = true;
-        }
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(device);
-    }
+    Slot* const S = F.S;
     int rc = SFMX_OK;
     {
         // the pair offsets on the host: they size the scratch
@@ -422,8 +392,8 @@ int sfmx_relative_poses(const sfmx_point2f* const* keypoints, const int32_t* n_k
         std::vector<double> nanv;
         int64_t n = 0, nk = 0, longest = 0;
         if (inputs_on_device) {
-            PCHK(hipMemcpyAsync(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
-            PCHK(hipStreamSynchronize(st));
+            SFMX_HIP_CHK(hipMemcpyAsync(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
         } else {
             std::memcpy(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1));
         }
@@ -438,15 +408,15 @@ int sfmx_relative_poses(const sfmx_point2f* const* keypoints, const int32_t* n_k
             nanv.assign((size_t)21 * n_pairs, std::nan(""));
             for (double& v : nanv) { const uint64_t b = 0x7FF8000000000000ull; std::memcpy(&v, &b, 8); }
             if (inputs_on_device) {
-                PCHK(hipMemsetAsync(out_pair_offsets, 0, sizeof(int64_t) * (n_pairs + 1), st));
+                SFMX_HIP_CHK(hipMemsetAsync(out_pair_offsets, 0, sizeof(int64_t) * (n_pairs + 1), st));
                 if (n_pairs) {
-                    PCHK(hipMemsetAsync(out_status, 0, sizeof(int32_t) * n_pairs, st));
-                    PCHK(hipMemsetAsync(out_n_ransac_inliers, 0, sizeof(int32_t) * n_pairs, st));
-                    PCHK(hipMemsetAsync(out_n_inliers, 0, sizeof(int32_t) * n_pairs, st));
-                    PCHK(hipMemcpyAsync(out_E, nanv.data(), sizeof(double) * 9 * n_pairs, hipMemcpyHostToDevice, st));
-                    PCHK(hipMemcpyAsync(out_pose, nanv.data(), sizeof(double) * 12 * n_pairs, hipMemcpyHostToDevice, st));
+                    SFMX_HIP_CHK(hipMemsetAsync(out_status, 0, sizeof(int32_t) * n_pairs, st));
+                    SFMX_HIP_CHK(hipMemsetAsync(out_n_ransac_inliers, 0, sizeof(int32_t) * n_pairs, st));
+                    SFMX_HIP_CHK(hipMemsetAsync(out_n_inliers, 0, sizeof(int32_t) * n_pairs, st));
+                    SFMX_HIP_CHK(hipMemcpyAsync(out_E, nanv.data(), sizeof(double) * 9 * n_pairs, hipMemcpyHostToDevice, st));
+                    SFMX_HIP_CHK(hipMemcpyAsync(out_pose, nanv.data(), sizeof(double) * 12 * n_pairs, hipMemcpyHostToDevice, st));
                 }
-                PCHK(hipStreamSynchronize(st));
+                SFMX_HIP_CHK(hipStreamSynchronize(st));
             } else {
                 std::memset(out_pair_offsets, 0, sizeof(int64_t) * (n_pairs + 1));
                 if (n_pairs) {
@@ -477,61 +447,38 @@ int sfmx_relative_poses(const sfmx_point2f* const* keypoints, const int32_t* n_k
         {
             // device block: [shot table | pair table | result words | correspondence scratch (only with a list over
             // CAP) | candidate bits | (host inputs: keypoints, matches, offsets, every output)]
-            const bool H = !inputs_on_device;
-            const size_t b_sh = r256(sizeof(ShotP) * n_shots), b_pr = r256(sizeof(PairP) * n_pairs), b_res = 256,
-                         b_scr = longest > CAP ? r256(sizeof(double) * 4 * n) : 0, b_cb = r256((size_t)n);
-            const size_t b_kd = H ? r256(sizeof(float2) * nk) : 0, b_md = H ? r256(sizeof(sfmx_dmatch) * n) : 0,
-                         b_od = H ? r256(sizeof(int64_t) * (n_pairs + 1)) : 0, b_os = H ? r256(sizeof(int32_t) * n_pairs) : 0,
-                         b_oe = H ? r256(sizeof(double) * 9 * n_pairs) : 0, b_op = H ? r256(sizeof(double) * 12 * n_pairs) : 0,
-                         b_ok = H ? r256((size_t)n) : 0, b_or = H ? r256(sizeof(int32_t) * n_pairs) : 0,
-                         b_oi = H ? r256(sizeof(int32_t) * n_pairs) : 0, b_om = H ? r256(sizeof(sfmx_dmatch) * n) : 0,
-                         b_oo = H ? r256(sizeof(int64_t) * (n_pairs + 1)) : 0;
-            const size_t need = b_sh + b_pr + b_res + b_scr + b_cb + b_kd + b_md + b_od + b_os + b_oe + b_op + b_ok + b_or +
-                                b_oi + b_om + b_oo;
-            if (S->dev_cap < need) {
-                if (S->dev) (void)hipFree(S->dev);
-                S->dev = nullptr;
-                S->dev_cap = 0;
-                if (hipMalloc(reinterpret_cast<void**>(&S->dev), need + need / 4) != hipSuccess) {
-                    S->dev = nullptr;
-                    (void)hipGetLastError();
-                    rc = SFMX_ENOMEM;
-                    goto done;
-                }
-                S->dev_cap = need + need / 4;
-            }
-            const size_t need_pin = b_sh + b_pr + b_res;
-            if (S->pin_cap < need_pin) {
-                if (S->pin) (void)hipHostFree(S->pin);
-                S->pin = nullptr;
-                S->pin_cap = 0;
-                if (hipHostMalloc(reinterpret_cast<void**>(&S->pin), need_pin + need_pin / 4, hipHostMallocDefault) != hipSuccess) {
-                    S->pin = nullptr;
-                    rc = SFMX_ENOMEM;
-                    goto done;
-                }
-                S->pin_cap = need_pin + need_pin / 4;
-            }
-            if (!S->e0 && (hipEventCreate(&S->e0) != hipSuccess || hipEventCreate(&S->e1) != hipSuccess)) { rc = SFMX_EDEVICE; goto done; }
-            char* d = S->dev;
-            ShotP* shd = reinterpret_cast<ShotP*>(d);                    d += b_sh;
-            PairP* prd = reinterpret_cast<PairP*>(d);                    d += b_pr;
-            int64_t* resd = reinterpret_cast<int64_t*>(d);               d += b_res;
-            double* scr = b_scr ? reinterpret_cast<double*>(d) : nullptr; d += b_scr;
-            uint8_t* cbd = reinterpret_cast<uint8_t*>(d);                d += b_cb;
-            float2* kd = reinterpret_cast<float2*>(d);                   d += b_kd;
-            sfmx_dmatch* md = reinterpret_cast<sfmx_dmatch*>(d);         d += b_md;
-            int64_t* od = reinterpret_cast<int64_t*>(d);                 d += b_od;
-            int32_t* osd = reinterpret_cast<int32_t*>(d);                d += b_os;
-            double* oed = reinterpret_cast<double*>(d);                  d += b_oe;
-            double* opd = reinterpret_cast<double*>(d);                  d += b_op;
-            uint8_t* okd = reinterpret_cast<uint8_t*>(d);                d += b_ok;
-            int32_t* ord_ = reinterpret_cast<int32_t*>(d);               d += b_or;
-            int32_t* oid = reinterpret_cast<int32_t*>(d);                d += b_oi;
-            sfmx_dmatch* omd = reinterpret_cast<sfmx_dmatch*>(d);        d += b_om;
-            int64_t* ood = reinterpret_cast<int64_t*>(d);
+            const bool H = F.host;
+            const size_t np = (size_t)n_pairs;
+            BlockLayout L;
+            ShotP* shd;
+            PairP* prd;
+            int64_t *resd, *od, *ood;
+            double *scr, *oed, *opd;
+            uint8_t *cbd, *okd;
+            float2* kd;
+            sfmx_dmatch *md, *omd;
+            int32_t *osd, *ord_, *oid;
+            L.want(shd, n_shots);
+            L.want(prd, np);
+            L.want(resd, 2);
+            const size_t b_tab = L.need;   // up to here: staged in pinned memory, one upload
+            L.want(scr, 4 * n, longest > CAP);
+            L.want(cbd, n);
+            L.want(kd, nk, H);
+            L.want(md, n, H);
+            L.want(od, np + 1, H);
+            L.want(osd, np, H);
+            L.want(oed, 9 * np, H);
+            L.want(opd, 12 * np, H);
+            L.want(okd, n, H);
+            L.want(ord_, np, H);
+            L.want(oid, np, H);
+            L.want(omd, n, H);
+            L.want(ood, np + 1, H);
+            rc = F.reserve(L, b_tab);
+            if (rc != SFMX_OK) goto done;
             // shot table: camera and keypoint pointer of every shot
-            ShotP* hs = reinterpret_cast<ShotP*>(S->pin);
+            ShotP* hs = F.pinned(shd);
             int64_t o = 0;
             for (int i = 0; i < n_shots; ++i) {
                 const sfmx_tri_camera& c = cameras[shot_camera[i]];
@@ -540,14 +487,14 @@ int sfmx_relative_poses(const sfmx_point2f* const* keypoints, const int32_t* n_k
                 t.nkp = n_keypoints[i];
                 t._pad = 0;
                 if (H) {
-                    if (n_keypoints[i]) PCHK(hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st));
+                    if (n_keypoints[i]) SFMX_HIP_CHK(hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st));
                     t.kp = kd + o;
                     o += n_keypoints[i];
                 } else {
                     t.kp = reinterpret_cast<const float2*>(keypoints[i]);
                 }
             }
-            PairP* hp = reinterpret_cast<PairP*>(S->pin + b_sh);
+            PairP* hp = F.pinned(prd);
             for (int p = 0; p < n_pairs; ++p) {
                 const int L = pairs[2 * p], R = pairs[2 * p + 1];
                 // SfM.cpp:515-521; the right width is never looked at (:519)
@@ -556,57 +503,45 @@ int sfmx_relative_poses(const sfmx_point2f* const* keypoints, const int32_t* n_k
                                                              shot_size[2 * R + 1]}) * threshold;
                 hp[p] = PairP{L, R, thr};
             }
-            int64_t* hres = reinterpret_cast<int64_t*>(S->pin + b_sh + b_pr);
+            int64_t* hres = F.pinned(resd);
             hres[0] = hres[1] = 0;
-            PCHK(hipMemcpyAsync(S->dev, S->pin, b_sh + b_pr + b_res, hipMemcpyHostToDevice, st));   // tables, result words = 0
-            const DMatchDev* dm = reinterpret_cast<const DMatchDev*>(matches);
-            const int64_t* doff = pair_offsets;
-            int32_t *dst = out_status, *dnr = out_n_ransac_inliers, *dni = out_n_inliers;
-            double *dE = out_E, *dP = out_pose;
-            uint8_t* dk = out_mask;
-            DMatchDev* dom = reinterpret_cast<DMatchDev*>(out_matches);
-            int64_t* doo = out_pair_offsets;
-            if (H) {
-                PCHK(hipMemcpyAsync(md, matches, sizeof(sfmx_dmatch) * n, hipMemcpyHostToDevice, st));
-                PCHK(hipMemcpyAsync(od, pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyHostToDevice, st));
-                dm = reinterpret_cast<const DMatchDev*>(md);
-                doff = od; dst = osd; dnr = ord_; dni = oid; dE = oed; dP = opd; dk = okd;
-                dom = reinterpret_cast<DMatchDev*>(omd);
-                doo = ood;
-            }
+            SFMX_HIP_CHK(F.upload(b_tab));   // tables, result words = 0
+            const DMatchDev* dm = reinterpret_cast<const DMatchDev*>(F.in(matches, md, n));
+            const int64_t* doff = F.in(pair_offsets, od, np + 1);
+            SFMX_HIP_CHK(F.err);
+            int32_t *dst = F.out(out_status, osd), *dnr = F.out(out_n_ransac_inliers, ord_), *dni = F.out(out_n_inliers, oid);
+            double *dE = F.out(out_E, oed), *dP = F.out(out_pose, opd);
+            uint8_t* dk = F.out(out_mask, okd);
+            DMatchDev* dom = reinterpret_cast<DMatchDev*>(F.out(out_matches, omd));
+            int64_t* doo = F.out(out_pair_offsets, ood);
             (void)hipEventRecord(S->e0, st);
             pose_pair_kernel<<<(unsigned)n_pairs, BLOCK, 0, st>>>(shd, prd, dm, doff, scr, n, cbd, max_iters, confidence, dst, dE,
                                                                   dP, dk, dnr, dni, resd);
             pose_scan_kernel<<<1, 1024, 0, st>>>(dni, n_pairs, doo, resd);
             pose_compact_kernel<<<(unsigned)n_pairs, BLOCK, 0, st>>>(dm, doff, dk, doo, dom);
             (void)hipEventRecord(S->e1, st);
-            PCHK(hipGetLastError());
-            PCHK(hipMemcpyAsync(hres, resd, sizeof(int64_t) * 2, hipMemcpyDeviceToHost, st));   // total and the index flag
-            PCHK(hipStreamSynchronize(st));
+            SFMX_HIP_CHK(hipGetLastError());
+            SFMX_HIP_CHK(hipMemcpyAsync(hres, resd, sizeof(int64_t) * 2, hipMemcpyDeviceToHost, st));   // total and the index flag
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
             if (hres[1] != 0) { set_last_error("match index outside its image's keypoints"); rc = SFMX_EINVAL; goto done; }
             const int64_t total = hres[0];
             if (total < 0 || total > n) { set_last_error("inlier count self check failed"); rc = SFMX_EINTERNAL; goto done; }
-            if (H) {
-                PCHK(hipMemcpyAsync(out_status, osd, sizeof(int32_t) * n_pairs, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_E, oed, sizeof(double) * 9 * n_pairs, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_pose, opd, sizeof(double) * 12 * n_pairs, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_mask, okd, (size_t)n, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_n_ransac_inliers, ord_, sizeof(int32_t) * n_pairs, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_n_inliers, oid, sizeof(int32_t) * n_pairs, hipMemcpyDeviceToHost, st));
-                if (total) PCHK(hipMemcpyAsync(out_matches, omd, sizeof(sfmx_dmatch) * total, hipMemcpyDeviceToHost, st));
-                PCHK(hipMemcpyAsync(out_pair_offsets, ood, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
-                PCHK(hipStreamSynchronize(st));
-            }
+            SFMX_HIP_CHK(F.back(out_status, osd, np));
+            SFMX_HIP_CHK(F.back(out_E, oed, 9 * np));
+            SFMX_HIP_CHK(F.back(out_pose, opd, 12 * np));
+            SFMX_HIP_CHK(F.back(out_mask, okd, n));
+            SFMX_HIP_CHK(F.back(out_n_ransac_inliers, ord_, np));
+            SFMX_HIP_CHK(F.back(out_n_inliers, oid, np));
+            if (total) SFMX_HIP_CHK(F.back(out_matches, omd, total));
+            SFMX_HIP_CHK(F.back(out_pair_offsets, ood, np + 1));
+            if (H) SFMX_HIP_CHK(hipStreamSynchronize(st));
             float ms = -1.f;
             (void)hipEventElapsedTime(&ms, S->e0, S->e1);
             g_last_ms = ms;
         }
     done:;
-        if (rc != SFMX_OK && S) (void)hipStreamSynchronize(st);   // nothing in flight from the pinned staging
+        rc = F.finish(rc, "sfmx_relative_poses");
     }
-    if (rc == SFMX_EDEVICE) set_last_error("HIP error in sfmx_relative_poses");
-    if (rc == SFMX_ENOMEM) set_last_error("device allocation failed");
-    if (prev >= 0) (void)hipSetDevice(prev);
     return rc;
 }
 

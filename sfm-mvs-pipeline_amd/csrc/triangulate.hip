@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/sfmx_triangulate.h"
+#include "device_call.hpp"
 #include "match_common.hpp"
 
 namespace sfmx {
@@ -355,28 +356,13 @@ void tri_compact_kernel(const int32_t* __restrict__ pairs, int n_pairs, const in
 
 thread_local float g_last_ms = -1.f;
 
-// Per device, kept between calls (as homography.hip): the device check's result, one device block for the
-// call's tables and scratch (regrown with headroom), pinned staging for the small uploads and the result
-// words, two timing events.
-struct Slot {
-    bool checked = false;
-    char* dev = nullptr;
-    size_t dev_cap = 0;
-    char* pin = nullptr;
-    size_t pin_cap = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    std::mutex mu;   // one call per device at a time
-};
-Slot g_slot[64];
-size_t r256(size_t b) { return (std::max<size_t>(b, 1) + 255) & ~(size_t)255; }
+Slot g_slot[64];   // csrc/device_call.hpp
 
 }  // namespace tri
 }  // namespace sfmx
 
 using namespace sfmx;
 using namespace sfmx::tri;
-
-#define TCHK(expr) do { if ((expr) != hipSuccess) { rc = SFMX_EDEVICE; goto done; } } while (0)
 
 extern "C" {
 
@@ -407,37 +393,21 @@ int sfmx_triangulate_matches(const sfmx_point2f* const* keypoints, const int32_t
             set_last_error("pair shot index out of range");
             return SFMX_EINVAL;
         }
-    const hipStream_t st = (hipStream_t)stream;
-    Slot* S = nullptr;
-    int prev = -1;
+    DeviceCall F(stream, !inputs_on_device);
+    const hipStream_t st = F.st;
     if (inputs_on_device || pair_offsets[n_pairs] != 0) {   // anything but an empty host call needs the device
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_last_error("no HIP device visible"); return SFMX_EDEVICE; }
-        if (device < 0 || device >= ndev || device >= 64) { set_last_error("device index out of range"); return SFMX_EINVAL; }
-        S = &g_slot[device];
+        const int orc = F.open(g_slot, device);
+        if (orc != SFMX_OK) return orc;
     }
-    std::unique_lock<std::mutex> lock;
-    if (S) {
-        lock = std::unique_lock<std::mutex>(S->mu);
-        if (!S->checked) {
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-                set_last_error("sfmx kernels are built for gfx950 only");
-                return SFMX_EDEVICE;
-            }
-            S->checked = true;
-        }
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(device);
-    }
+    Slot* const S = F.S;
     int rc = SFMX_OK;
     {
         // the pair offsets on the host: they size the launch
         std::vector<int64_t> hoff(n_pairs + 1);
         int64_t n = 0, n_blocks = 0, nk = 0;
         if (inputs_on_device) {
-            TCHK(hipMemcpyAsync(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
-            TCHK(hipStreamSynchronize(st));
+            SFMX_HIP_CHK(hipMemcpyAsync(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
         } else {
             std::memcpy(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1));
         }
@@ -447,8 +417,8 @@ int sfmx_triangulate_matches(const sfmx_point2f* const* keypoints, const int32_t
         n = hoff[n_pairs];
         if (n == 0) {   // no match: nothing is launched
             if (inputs_on_device) {
-                TCHK(hipMemsetAsync(out_point_offsets, 0, sizeof(int64_t) * (n_pairs + 1), st));
-                TCHK(hipStreamSynchronize(st));
+                SFMX_HIP_CHK(hipMemsetAsync(out_point_offsets, 0, sizeof(int64_t) * (n_pairs + 1), st));
+                SFMX_HIP_CHK(hipStreamSynchronize(st));
             } else {
                 std::memset(out_point_offsets, 0, sizeof(int64_t) * (n_pairs + 1));
             }
@@ -478,63 +448,38 @@ int sfmx_triangulate_matches(const sfmx_point2f* const* keypoints, const int32_t
         {
             // device block: [shot table | pairs | result words | block counts | block offsets | keep masks |
             // xyz scratch | keypoint scratch | (host inputs: keypoints, matches, offsets, every output)]
-            const bool H = !inputs_on_device;
-            const size_t b_sh = r256(sizeof(ShotT) * n_shots), b_pr = r256(sizeof(int32_t) * 2 * n_pairs), b_res = 256,
-                         b_bc = r256(sizeof(int32_t) * n_blocks), b_bo = r256(sizeof(int64_t) * n_blocks),
-                         b_km = r256(sizeof(unsigned long long) * n_blocks * (BLOCK / 64)),
-                         b_s1 = r256(sizeof(float4) * n), b_s2 = r256(sizeof(float4) * n);
-            const size_t b_kd = H ? r256(sizeof(float2) * nk) : 0, b_md = H ? r256(sizeof(sfmx_dmatch) * n) : 0,
-                         b_od = H ? r256(sizeof(int64_t) * (n_pairs + 1)) : 0,
-                         b_po = H ? r256(sizeof(int64_t) * (n_pairs + 1)) : 0, b_ox = H ? r256(sizeof(double) * 3 * n) : 0,
-                         b_om = H ? r256(sizeof(int64_t) * n) : 0, b_os = H ? r256(sizeof(int32_t) * 2 * n) : 0,
-                         b_oy = H ? r256(sizeof(double) * 4 * n) : 0, b_oe = H && out_err ? r256(sizeof(double) * 2 * n) : 0;
-            const size_t need = b_sh + b_pr + b_res + b_bc + b_bo + b_km + b_s1 + b_s2 + b_kd + b_md + b_od + b_po + b_ox +
-                                b_om + b_os + b_oy + b_oe;
-            if (S->dev_cap < need) {
-                if (S->dev) (void)hipFree(S->dev);
-                S->dev = nullptr;
-                S->dev_cap = 0;
-                if (hipMalloc(reinterpret_cast<void**>(&S->dev), need + need / 4) != hipSuccess) {
-                    S->dev = nullptr;
-                    (void)hipGetLastError();
-                    rc = SFMX_ENOMEM;
-                    goto done;
-                }
-                S->dev_cap = need + need / 4;
-            }
-            const size_t need_pin = b_sh + b_pr + b_res;
-            if (S->pin_cap < need_pin) {
-                if (S->pin) (void)hipHostFree(S->pin);
-                S->pin = nullptr;
-                S->pin_cap = 0;
-                if (hipHostMalloc(reinterpret_cast<void**>(&S->pin), need_pin + need_pin / 4, hipHostMallocDefault) != hipSuccess) {
-                    S->pin = nullptr;
-                    rc = SFMX_ENOMEM;
-                    goto done;
-                }
-                S->pin_cap = need_pin + need_pin / 4;
-            }
-            if (!S->e0 && (hipEventCreate(&S->e0) != hipSuccess || hipEventCreate(&S->e1) != hipSuccess)) { rc = SFMX_EDEVICE; goto done; }
-            char* d = S->dev;
-            ShotT* shd = reinterpret_cast<ShotT*>(d);                                  d += b_sh;
-            int32_t* prd = reinterpret_cast<int32_t*>(d);                              d += b_pr;
-            int64_t* resd = reinterpret_cast<int64_t*>(d);                             d += b_res;
-            int32_t* bcd = reinterpret_cast<int32_t*>(d);                              d += b_bc;
-            int64_t* bod = reinterpret_cast<int64_t*>(d);                              d += b_bo;
-            unsigned long long* kmd = reinterpret_cast<unsigned long long*>(d);        d += b_km;
-            float4* s1 = reinterpret_cast<float4*>(d);                                 d += b_s1;
-            float4* s2 = reinterpret_cast<float4*>(d);                                 d += b_s2;
-            float2* kd = reinterpret_cast<float2*>(d);                                 d += b_kd;
-            sfmx_dmatch* md = reinterpret_cast<sfmx_dmatch*>(d);                       d += b_md;
-            int64_t* od = reinterpret_cast<int64_t*>(d);                               d += b_od;
-            int64_t* pod = reinterpret_cast<int64_t*>(d);                              d += b_po;
-            double* oxd = reinterpret_cast<double*>(d);                                d += b_ox;
-            int64_t* omd = reinterpret_cast<int64_t*>(d);                              d += b_om;
-            int32_t* osd = reinterpret_cast<int32_t*>(d);                              d += b_os;
-            double* oyd = reinterpret_cast<double*>(d);                                d += b_oy;
-            double* oed = reinterpret_cast<double*>(d);
+            const bool H = F.host;
+            BlockLayout L;
+            ShotT* shd;
+            int32_t *prd, *bcd, *osd;
+            int64_t *resd, *bod, *od, *pod, *omd;
+            unsigned long long* kmd;
+            float4 *s1, *s2;
+            float2* kd;
+            sfmx_dmatch* md;
+            double *oxd, *oyd, *oed;
+            L.want(shd, n_shots);
+            L.want(prd, 2 * (size_t)n_pairs);
+            L.want(resd, 2);
+            const size_t b_tab = L.need;   // up to here: staged in pinned memory, one upload
+            L.want(bcd, n_blocks);
+            L.want(bod, n_blocks);
+            L.want(kmd, n_blocks * (BLOCK / 64));
+            L.want(s1, n);
+            L.want(s2, n);
+            L.want(kd, nk, H);
+            L.want(md, n, H);
+            L.want(od, n_pairs + 1, H);
+            L.want(pod, n_pairs + 1, H);
+            L.want(oxd, 3 * n, H);
+            L.want(omd, n, H);
+            L.want(osd, 2 * n, H);
+            L.want(oyd, 4 * n, H);
+            L.want(oed, 2 * n, H && out_err);
+            rc = F.reserve(L, b_tab);
+            if (rc != SFMX_OK) goto done;
             // shot table: pose, camera and keypoint pointer of every shot
-            ShotT* hs = reinterpret_cast<ShotT*>(S->pin);
+            ShotT* hs = F.pinned(shd);
             int64_t o = 0;
             for (int i = 0; i < n_shots; ++i) {
                 const sfmx_tri_camera& c = cameras[shot_camera[i]];
@@ -546,64 +491,52 @@ int sfmx_triangulate_matches(const sfmx_point2f* const* keypoints, const int32_t
                 t.nkp = n_keypoints[i];
                 t._pad = 0;
                 if (H) {
-                    if (n_keypoints[i]) TCHK(hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st));
+                    if (n_keypoints[i]) SFMX_HIP_CHK(hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st));
                     t.kp = kd + o;
                     o += n_keypoints[i];
                 } else {
                     t.kp = reinterpret_cast<const float2*>(keypoints[i]);
                 }
             }
-            std::memcpy(S->pin + b_sh, pairs, sizeof(int32_t) * 2 * n_pairs);
-            int64_t* hres = reinterpret_cast<int64_t*>(S->pin + b_sh + b_pr);
+            std::memcpy(F.pinned(prd), pairs, sizeof(int32_t) * 2 * n_pairs);
+            int64_t* hres = F.pinned(resd);
             hres[0] = hres[1] = 0;
-            TCHK(hipMemcpyAsync(S->dev, S->pin, b_sh + b_pr + b_res, hipMemcpyHostToDevice, st));   // tables, result words = 0
-            const DMatchDev* dm = reinterpret_cast<const DMatchDev*>(matches);
-            const int64_t* doff = pair_offsets;
-            int64_t* dpo = out_point_offsets;
-            double *dox = out_xyz, *doy = out_origin_xy, *doe = out_err;
-            int64_t* dom = out_match;
-            int32_t* dos = out_origin_shot;
-            if (H) {
-                TCHK(hipMemcpyAsync(md, matches, sizeof(sfmx_dmatch) * n, hipMemcpyHostToDevice, st));
-                TCHK(hipMemcpyAsync(od, pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyHostToDevice, st));
-                dm = reinterpret_cast<const DMatchDev*>(md);
-                doff = od; dpo = pod; dox = oxd; dom = omd; dos = osd; doy = oyd;
-                doe = out_err ? oed : nullptr;
-            }
+            SFMX_HIP_CHK(F.upload(b_tab));   // tables, result words = 0
+            const DMatchDev* dm = reinterpret_cast<const DMatchDev*>(F.in(matches, md, n));
+            const int64_t* doff = F.in(pair_offsets, od, n_pairs + 1);
+            SFMX_HIP_CHK(F.err);
+            int64_t *dpo = F.out(out_point_offsets, pod), *dom = F.out(out_match, omd);
+            double *dox = F.out(out_xyz, oxd), *doy = F.out(out_origin_xy, oyd), *doe = F.out(out_err, oed);
+            int32_t* dos = F.out(out_origin_shot, osd);
             (void)hipEventRecord(S->e0, st);
             tri_solve_kernel<<<(unsigned)n_blocks, BLOCK, 0, st>>>(shd, prd, n_pairs, dm, doff, n, max_reprojection_error, s1, s2,
                                                                    kmd, bcd, doe, resd);
             tri_scan_kernel<<<1, 1024, 0, st>>>(bcd, n_blocks, bod, kmd, doff, n_pairs, n, dpo, resd);
             tri_compact_kernel<<<(unsigned)n_blocks, BLOCK, 0, st>>>(prd, n_pairs, doff, n, s1, s2, kmd, bod, dox, dom, dos, doy);
             (void)hipEventRecord(S->e1, st);
-            TCHK(hipGetLastError());
-            TCHK(hipMemcpyAsync(hres, resd, sizeof(int64_t) * 2, hipMemcpyDeviceToHost, st));   // total and the index flag
-            TCHK(hipStreamSynchronize(st));
+            SFMX_HIP_CHK(hipGetLastError());
+            SFMX_HIP_CHK(hipMemcpyAsync(hres, resd, sizeof(int64_t) * 2, hipMemcpyDeviceToHost, st));   // total and the index flag
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
             if (hres[1] != 0) { set_last_error("match index outside its image's keypoints"); rc = SFMX_EINVAL; goto done; }
             const int64_t total = hres[0];
             if (total < 0 || total > n) { set_last_error("point count self check failed"); rc = SFMX_EINTERNAL; goto done; }
-            if (H) {
-                TCHK(hipMemcpyAsync(out_point_offsets, pod, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
-                if (total) {
-                    TCHK(hipMemcpyAsync(out_xyz, oxd, sizeof(double) * 3 * total, hipMemcpyDeviceToHost, st));
-                    TCHK(hipMemcpyAsync(out_match, omd, sizeof(int64_t) * total, hipMemcpyDeviceToHost, st));
-                    TCHK(hipMemcpyAsync(out_origin_shot, osd, sizeof(int32_t) * 2 * total, hipMemcpyDeviceToHost, st));
-                    TCHK(hipMemcpyAsync(out_origin_xy, oyd, sizeof(double) * 4 * total, hipMemcpyDeviceToHost, st));
-                }
-                if (out_err) TCHK(hipMemcpyAsync(out_err, oed, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, st));
-                TCHK(hipStreamSynchronize(st));
+            SFMX_HIP_CHK(F.back(out_point_offsets, pod, n_pairs + 1));
+            if (total) {
+                SFMX_HIP_CHK(F.back(out_xyz, oxd, 3 * total));
+                SFMX_HIP_CHK(F.back(out_match, omd, total));
+                SFMX_HIP_CHK(F.back(out_origin_shot, osd, 2 * total));
+                SFMX_HIP_CHK(F.back(out_origin_xy, oyd, 4 * total));
             }
+            if (out_err) SFMX_HIP_CHK(F.back(out_err, oed, 2 * n));
+            if (H) SFMX_HIP_CHK(hipStreamSynchronize(st));
             *out_n_points = total;
             float ms = -1.f;
             (void)hipEventElapsedTime(&ms, S->e0, S->e1);
             g_last_ms = ms;
         }
     done:;
-        if (rc != SFMX_OK && S) (void)hipStreamSynchronize(st);   // nothing in flight from the pinned staging
+        rc = F.finish(rc, "sfmx_triangulate_matches");
     }
-    if (rc == SFMX_EDEVICE) set_last_error("HIP error in sfmx_triangulate_matches");
-    if (rc == SFMX_ENOMEM) set_last_error("device allocation failed");
-    if (prev >= 0) (void)hipSetDevice(prev);
     return rc;
 }
 

@@ -16,6 +16,7 @@ import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -63,12 +64,15 @@ def main():
         sys.exit("cloud_bench: no GPU visible (there is no CPU path to time)")
     x = torch.from_numpy(surface_cloud(a.points, a.seed)).cuda()
     n = x.shape[0]
-    ms, st = [], {}
+    ms, wall, st = [], [], {}
     for i in range(a.warmup + a.steps):
-        d, nb = cloud.neighbor_distances(x, a.max_equal, neighbors=True)
+        t0 = time.perf_counter()
+        d, nb = cloud.neighbor_distances(x, a.max_equal, neighbors=True)   # returns after its stream synchronised
+        w = (time.perf_counter() - t0) * 1e3
         st = cloud.last_stats()
         if i >= a.warmup:
             ms.append(st["kernel_ms"])
+            wall.append(w)
     t = float(np.median(ms)) * 1e-3
     cells = 16 * min(max(n, 64), 1 << 23) + 2
     touched = n * (7 * 12 + 3 * 8 + 2 * 16 + 16) + cells * 4
@@ -76,6 +80,7 @@ def main():
     print(json.dumps({
         "tool": "cloud_bench", "points": n, "max_equal": a.max_equal, "steps": a.steps, "warmup": a.warmup,
         "kernel_ms": round(t * 1e3, 4), "kernel_ms_min": round(min(ms), 4), "kernel_ms_max": round(max(ms), 4),
+        "call_wall_ms": round(float(np.median(wall)), 4),
         "points_per_s": round(n / t, 1), "evaluations_per_point": round(st["evaluations"] / n, 2),
         "brute_queries": st["brute_queries"], "bytes_touched": touched,
         "hbm_frac": round(touched / t / (HBM_PEAK_GBS * 1e9), 4),
