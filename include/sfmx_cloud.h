@@ -82,7 +82,9 @@ int sfmx_cloud_last_stats(float* kernel_ms, int64_t* evaluations, int64_t* brute
  * mean and variance are sequential double sums in sorted order, the variance
  * over (size - 1) with (x - mean) * (x - mean) for pow(x - mean, 2); the median
  * is the middle element or the mean of the two middle ones; an empty list gives
- * zeros.  n_points is carried into the record (the N_Points column). */
+ * zeros.  n_points is carried into the record (the N_Points column).  NaN
+ * elements (reprojection errors, sfmx_report.h; distances have none) stand
+ * behind the ordered ones: the reference's sort is undefined on them. */
 typedef struct sfmx_cloud_stats {
     int64_t n_points;
     double max, min, mean, median, variance, deviation;

@@ -25,11 +25,11 @@ struct Stats { int64_t n_points; double max, min, mean, median, variance, deviat
 
 // MathUtils.h:53-90, bug for bug: min and max start at 0, the sums run in sorted order, the variance
 // divides by size - 1 (NaN for one element).  pow(x - mean, 2) is the product (x - mean) * (x - mean).
-inline Stats statistics(const double* d, int64_t n, int64_t n_points) {
+// The part behind the sort, on a list that is already in order (csrc/report_host.hpp sorts its own).
+inline Stats statistics_sorted(const std::vector<double>& v, int64_t n_points) {
     Stats s{n_points, 0, 0, 0, 0, 0, 0};
+    const int64_t n = (int64_t)v.size();
     if (n <= 0) return s;
-    std::vector<double> v(d, d + n);
-    std::sort(v.begin(), v.end(), [](double a, double b) { return a < b; });
     double mn = 0, mx = 0, mean = 0, var = 0;
     for (double x : v) {
         mn = std::min(mn, x);
@@ -49,6 +49,21 @@ inline Stats statistics(const double* d, int64_t n, int64_t n_points) {
     s.deviation = std::sqrt(var);
     s.median = (n % 2 == 0) ? (v[n / 2] + v[n / 2 - 1]) / 2.0 : v[n / 2];
     return s;
+}
+
+// Ascending, NaNs behind the ordered values.  The reference's std::sort on a list with NaNs is undefined (its
+// comparison is no strict weak order); a list without NaNs is sorted exactly as before.  Distances are never
+// NaN; reprojection errors can be (include/sfmx_report.h).
+inline void sort_nan_last(std::vector<double>& v) {
+    const auto nan = std::partition(v.begin(), v.end(), [](double x) { return x == x; });
+    std::sort(v.begin(), nan, [](double a, double b) { return a < b; });
+}
+
+inline Stats statistics(const double* d, int64_t n, int64_t n_points) {
+    if (n <= 0) return Stats{n_points, 0, 0, 0, 0, 0, 0};
+    std::vector<double> v(d, d + n);
+    sort_nan_last(v);
+    return statistics_sorted(v, n_points);
 }
 
 // PclUtils.cpp:313-328.  resolution < 0: the variance of the list.  Keys ascend; distinct as doubles.

@@ -25,6 +25,7 @@
 #include "../../include/sfmx_triangulate.h"
 #include "device_call.hpp"
 #include "match_common.hpp"
+#include "project_device.hpp"
 
 namespace sfmx {
 namespace tri {
@@ -179,37 +180,10 @@ __device__ __forceinline__ void jacobi_null(double (&At)[4][4], float (&h)[4]) {
     for (int k = 0; k < 4; ++k) h[k] = (float)(r == 0 ? V[0][k] : (r == 1 ? V[1][k] : (r == 2 ? V[2][k] : V[3][k])));
 }
 
-// A NaN result leaves as the canonical quiet NaN: IEEE 754 leaves the sign and payload of a NaN open, and
-// x86 and gfx950 produce different ones.  On the bit patterns: the compiler folds `v != v ? NaN : v` to v.
-__device__ __forceinline__ float canon(float v) {
-    const uint32_t b = __float_as_uint(v);
-    return __uint_as_float((b & 0x7FFFFFFFu) > 0x7F800000u ? 0x7FC00000u : b);
-}
-__device__ __forceinline__ double canon(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return __longlong_as_double((long long)((b & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull ? 0x7FF8000000000000ull : b));
-}
-
-// cv::projectPoints with R, t of the pose, then the reprojection error against the keypoint
+// cv::projectPoints with R, t of the pose (project_device.hpp), then the reprojection error against the keypoint
 __device__ __forceinline__ double reproject_error(const ShotT* __restrict__ S, float Xf, float Yf, float Zf, const float2 pt) {
-    const double X = (double)Xf, Y = (double)Yf, Z = (double)Zf;
-    double x = S->P[0] * X + S->P[1] * Y + S->P[2] * Z + S->P[3];
-    double y = S->P[4] * X + S->P[5] * Y + S->P[6] * Z + S->P[7];
-    double z = S->P[8] * X + S->P[9] * Y + S->P[10] * Z + S->P[11];
-    z = z != 0 ? 1.0 / z : 1.0;
-    x = x * z;
-    y = y * z;
-    const double r2 = x * x + y * y;
-    const double r4 = r2 * r2;
-    const double r6 = r4 * r2;
-    const double a1 = 2.0 * x * y;
-    const double a2 = r2 + 2.0 * x * x;
-    const double a3 = r2 + 2.0 * y * y;
-    const double cdist = 1.0 + S->k1 * r2 + S->k2 * r4 + S->k3 * r6;
-    const double xd = x * cdist + S->p1 * a1 + S->p2 * a2;
-    const double yd = y * cdist + S->p1 * a3 + S->p2 * a1;
-    const float u = (float)(xd * S->fx + S->cx);
-    const float v = (float)(yd * S->fy + S->cy);
+    float u, v;
+    project_point(S, Xf, Yf, Zf, u, v);
     const float du = u - pt.x, dv = v - pt.y;
     const double e = sqrt((double)du * (double)du + (double)dv * (double)dv);
     return canon(e);

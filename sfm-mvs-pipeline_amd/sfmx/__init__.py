@@ -11,7 +11,11 @@ from .matching import (  # noqa: F401
     GridFeatureMatchingStrategy, calculate_shot_matches, match_pairs, pairs_unordered, pairs_video, pairs_grid,
 )
 
-from . import homography, scene, mvs, features, triangulate, pose, pnp, cloud  # noqa: F401,E402
+from . import homography, scene, mvs, features, triangulate, pose, pnp, cloud, report  # noqa: F401,E402
+from .report import (  # noqa: F401,E402
+    reprojection_errors, reprojection_errors_device, colorize_pointcloud, colorize_pointcloud_device,
+    writeToReprojectionErrorStatisticsCSV, writeToReprojectionErrorHistogramCSV, colorizePointcloud, writeToPLY,
+)
 from .triangulate import triangulate_matches, triangulate_matches_device, triangulateMatch  # noqa: F401,E402
 from .pose import relative_poses, relative_poses_device, findCameraPoseFromMatch  # noqa: F401,E402
 from .pnp import (  # noqa: F401,E402

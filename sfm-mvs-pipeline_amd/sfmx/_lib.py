@@ -101,7 +101,7 @@ class sfmx_cli_config(C.Structure):
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
 
-# Every symbol include/sfmx.h (and include/sfmx_ba.h, sfmx_homography.h, sfmx_triangulate.h, sfmx_pose.h, sfmx_pnp.h, sfmx_scene.h, sfmx_cloud.h) declares, with its ctypes prototype.
+# Every symbol include/sfmx.h (and include/sfmx_ba.h, sfmx_homography.h, sfmx_triangulate.h, sfmx_pose.h, sfmx_pnp.h, sfmx_scene.h, sfmx_cloud.h, sfmx_report.h) declares, with its ctypes prototype.
 _P = C.POINTER
 _i32p, _i64p, _vp = _P(C.c_int32), _P(C.c_int64), C.c_void_p
 PROTOTYPES = {
@@ -187,6 +187,17 @@ PROTOTYPES = {
     "sfmx_cloud_write_stats_csv": (C.c_int, [C.c_char_p, _P(sfmx_cloud_stats)]),
     "sfmx_cloud_write_neighbors_csv": (C.c_int, [C.c_char_p, _vp, _vp, C.c_int64]),
     "sfmx_cloud_write_quality_ply": (C.c_int, [C.c_char_p, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_double]),
+    # include/sfmx_report.h
+    "sfmx_reprojection_errors": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _P(sfmx_tri_camera), C.c_int32, _i32p,
+                                           _P(C.c_double), C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "sfmx_reprojection_last_kernel_ms": (C.c_float, []),
+    "sfmx_colorize_pointcloud": (C.c_int, [C.c_int64, _vp, _vp, _vp, C.c_int64, _P(_vp), _i32p, _i32p, _i64p, C.c_int32,
+                                           _vp, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "sfmx_colorize_last_kernel_ms": (C.c_float, []),
+    "sfmx_reprojection_write_stats_csv": (C.c_int, [C.c_char_p, _P(sfmx_cloud_stats)]),
+    "sfmx_reprojection_write_hist_csv": (C.c_int, [C.c_char_p, _vp, _vp, C.c_int64]),
+    "sfmx_write_pointcloud_ply": (C.c_int, [C.c_char_p, _vp, C.c_int64, _vp]),
+    "sfmx_write_cameras_ply": (C.c_int, [C.c_char_p, _vp, C.c_int32, _vp, C.c_int32, _vp, C.c_int32]),
     "sfmx_undistort_images": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "sfmx_sift_default_params": (None, [_vp]),
     "sfmx_sift_detect_compute": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, C.c_int32, C.c_int32, _vp, _vp,
