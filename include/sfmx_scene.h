@@ -50,6 +50,38 @@ int sfmx_find_3d2d_matches(const sfmx_point2f* const* keypoints, const int32_t* 
  * (table build + lookup kernels, HIP events on its stream); -1 before any call. */
 float sfmx_find_3d2d_last_kernel_ms(void);
 
+/* The candidate ranking of SfM::triangulate (sfm/SfM.cpp:276-300): the reference runs
+ * Scene::find3d2dMatches for every remaining shot and keeps the list sizes.  Here all
+ * candidates are counted in one call: one table build and one probe pass over the
+ * origin records.
+ *   pair_active[n_pairs]      a pair with 0 is invisible to the search; NULL: all visible
+ *   candidates[n_candidates]  shot indices, each at most once
+ *   out_count[c]              the number of origin records for which
+ *                             sfmx_find_3d2d_matches(shot = candidates[c]) over the visible
+ *                             pairs reports out_keypoint >= 0
+ * The tables are those of sfmx_find_3d2d_matches: for a candidate s and another shot o,
+ * the FIRST visible pair in list order joining {s, o}, keyed on the exact float bits of
+ * the keypoint position on o's side (-0 keyed as +0, NaN never matches), value the
+ * smallest match index.
+ * SFMX_EINVAL: a candidate or pair shot outside [0, n_shots), a candidate listed twice,
+ * pair or (host) origin offsets that do not ascend from 0, (host) a match index outside
+ * its image's keypoints in a pair that is read.  SFMX_ECAPACITY: 2^31 matches or more
+ * in the tables of one call (count the candidates in several calls), or one list of
+ * more than 2^29 matches.
+ * n_candidates == 0 writes nothing and touches no device.
+ * inputs_on_device = 1: keypoints[i], matches, pair_offsets, origin_* and out_count are
+ * device pointers on `device`; pairs, pair_active and candidates are host memory always. */
+int sfmx_count_3d2d_matches(const sfmx_point2f* const* keypoints, const int32_t* n_keypoints, int32_t n_shots,
+                            const int32_t* pairs, int32_t n_pairs, const int32_t* pair_active,
+                            const sfmx_dmatch* matches, const int64_t* pair_offsets, const int64_t* origin_offsets,
+                            int32_t n_points, const int32_t* origin_shot, const double* origin_xy,
+                            const int32_t* candidates, int32_t n_candidates, int32_t inputs_on_device, int32_t device,
+                            void* stream, int32_t* out_count);
+
+/* Device time (ms) of the last sfmx_count_3d2d_matches call on this thread (table
+ * build + count kernels, HIP events on its stream); 0 for n_candidates == 0, -1 before any call. */
+float sfmx_count_3d2d_last_kernel_ms(void);
+
 /* BundleAdjustment::doBundleAdjustment(const Scene&, ...)'s problem assembly
  * (common/BundleAdjustment.cpp:50-91) as flat sfmx_ba_problem arrays: one
  * observation per origin record, in point order then origin order (the

@@ -2,6 +2,7 @@
 // sfmx scene bookkeeping for gfx950.
 //
 //   sfmx_find_3d2d_matches            Scene::find3d2dMatches   (common/Scene.cpp:369-424)
+//   sfmx_count_3d2d_matches           the sizes of find3d2dMatches' lists for many shots at once (SfM.cpp:276-300)
 //   sfmx_ba_observations_from_origins BundleAdjustment.cpp:50-91 problem assembly (host, O(n))
 //
 // The reference's 3D-2D search is a nested linear scan: for every point
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "../../include/sfmx_scene.h"
+#include "device_call.hpp"
 #include "match_common.hpp"
 
 namespace sfmx {
@@ -40,7 +42,7 @@ struct UsedPair {          // a pair that is the first one joining {shot, other}
     int32_t other_is_left;  // 1: the other shot is the pair's left image (queryIdx side)
     int64_t table0;         // first slot of its table
     int32_t cap;            // table capacity (power of two)
-    int32_t _pad;
+    int32_t cand;           // sfmx_count_3d2d_matches: index of the candidate the table serves
 };
 
 __device__ __forceinline__ unsigned long long pos_key(float x, float y) {
@@ -133,7 +135,75 @@ void lookup_kernel(int64_t n_origins, const int32_t* __restrict__ origin_shot, c
     if (out_xy) { out_xy[2 * r] = res_xy.x; out_xy[2 * r + 1] = res_xy.y; }
 }
 
+// sfmx_count_3d2d_matches: one thread per origin record.  The tables of the candidates that have a pair with the
+// record's origin shot lie in used[tab_first[o] .. tab_first[o + 1]), ascending in candidate index; the thread
+// probes each of them with the record's position.  Hits are summed per wave in LDS (one row per wave, COUNT_TILE
+// candidates per pass; the walk of a lane stops at the pass's last candidate and goes on in the next pass), then
+// one global atomic per (wave, candidate with a hit).  16 KiB of LDS per block.
+constexpr int COUNT_TILE = 1024;
+
+__global__ __launch_bounds__(256)
+void count_kernel(int64_t n_origins, const int32_t* __restrict__ origin_shot, const double* __restrict__ origin_xy,
+                  int n_shots, const int32_t* __restrict__ tab_first, const UsedPair* __restrict__ used,
+                  const unsigned long long* __restrict__ tkey, const int32_t* __restrict__ tval,
+                  const int64_t* __restrict__ off, const DMatchDev* __restrict__ matches,
+                  const int32_t* __restrict__ nkp_cand, int n_candidates, int32_t* __restrict__ out_count) {
+    __shared__ int32_t cnt[4][COUNT_TILE];
+    const int lane = threadIdx.x & 63;
+    int32_t* const row = cnt[threadIdx.x >> 6];
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int e = 0, end = 0;
+    unsigned long long key = 0;
+    if (r < n_origins) {
+        const int o = origin_shot[r];
+        if (o >= 0 && o < n_shots) {
+            const double qx = origin_xy[2 * r], qy = origin_xy[2 * r + 1];
+            const float fx = (float)qx, fy = (float)qy;
+            if ((double)fx == qx && (double)fy == qy) {   // else no float keypoint position can equal it
+                e = tab_first[o];
+                end = tab_first[o + 1];
+                key = pos_key(fx, fy);
+            }
+        }
+    }
+    const uint32_t hash = mix(key);
+    for (int t0 = 0; t0 < n_candidates; t0 += COUNT_TILE) {
+        const int t1 = min(t0 + COUNT_TILE, n_candidates);
+        for (int j = lane; j < t1 - t0; j += 64) row[j] = 0;
+        __syncthreads();
+        while (e < end) {
+            const UsedPair u = used[e];
+            if (u.cand >= t1) break;
+            ++e;
+            uint32_t h = hash & (uint32_t)(u.cap - 1);
+            for (int probe = 0; probe < u.cap; ++probe) {
+                const unsigned long long k = tkey[u.table0 + h];
+                if (k == EMPTY) break;
+                if (k == key) {
+                    const int i = tval[u.table0 + h];
+                    const int64_t m0 = off[u.pair];
+                    if (i >= 0 && i < off[u.pair + 1] - m0) {
+                        const DMatchDev d = matches[m0 + i];
+                        const int sidx = u.other_is_left ? d.trainIdx : d.queryIdx;   // the candidate's side
+                        if (sidx >= 0 && sidx < nkp_cand[u.cand]) atomicAdd(&row[u.cand - t0], 1);
+                    }
+                    break;
+                }
+                h = (h + 1) & (uint32_t)(u.cap - 1);
+            }
+        }
+        __syncthreads();
+        for (int j = lane; j < t1 - t0; j += 64) {
+            const int v = row[j];
+            if (v) atomicAdd(out_count + t0 + j, v);
+        }
+        __syncthreads();
+    }
+}
+
 thread_local float g_last_ms = -1.f;
+thread_local float g_count_ms = -1.f;
+Slot g_count_slot[64];   // csrc/device_call.hpp
 
 struct Bufs {
     std::vector<void*> ptrs;
@@ -325,6 +395,205 @@ int sfmx_find_3d2d_matches(const sfmx_point2f* const* keypoints, const int32_t* 
     }
     if (rc == SFMX_ENOMEM) set_last_error("device allocation failed");
     if (prev >= 0) (void)hipSetDevice(prev);
+    return rc;
+}
+
+float sfmx_count_3d2d_last_kernel_ms(void) { return g_count_ms; }
+
+int sfmx_count_3d2d_matches(const sfmx_point2f* const* keypoints, const int32_t* n_keypoints, int32_t n_shots,
+                            const int32_t* pairs, int32_t n_pairs, const int32_t* pair_active,
+                            const sfmx_dmatch* matches, const int64_t* pair_offsets, const int64_t* origin_offsets,
+                            int32_t n_points, const int32_t* origin_shot, const double* origin_xy,
+                            const int32_t* candidates, int32_t n_candidates, int32_t inputs_on_device, int32_t device,
+                            void* stream, int32_t* out_count) {
+    if (n_shots < 0 || n_pairs < 0 || n_points < 0 || n_candidates < 0) { set_last_error("negative count"); return SFMX_EINVAL; }
+    if (!keypoints || !n_keypoints || (n_pairs && (!pairs || !pair_offsets)) || !origin_offsets ||
+        (n_candidates && (!candidates || !out_count))) {
+        set_last_error("null argument");
+        return SFMX_EINVAL;
+    }
+    for (int s = 0; s < n_shots; ++s)
+        if (n_keypoints[s] < 0) { set_last_error("negative keypoint count"); return SFMX_EINVAL; }
+    for (int p = 0; p < n_pairs; ++p)
+        if (pairs[2 * p] < 0 || pairs[2 * p] >= n_shots || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= n_shots) {
+            set_last_error("pair shot index out of range");
+            return SFMX_EINVAL;
+        }
+    std::vector<int32_t> cand_of_shot(n_shots, -1);
+    for (int c = 0; c < n_candidates; ++c) {
+        const int s = candidates[c];
+        if (s < 0 || s >= n_shots) { set_last_error("candidate shot index out of range"); return SFMX_EINVAL; }
+        if (cand_of_shot[s] >= 0) { set_last_error("candidate shot listed twice"); return SFMX_EINVAL; }
+        cand_of_shot[s] = c;
+    }
+    if (!inputs_on_device) {
+        if (origin_offsets[0] != 0) { set_last_error("origin offsets do not start at 0"); return SFMX_EINVAL; }
+        for (int p = 0; p < n_points; ++p)
+            if (origin_offsets[p + 1] < origin_offsets[p]) { set_last_error("origin offsets not ascending"); return SFMX_EINVAL; }
+        if (origin_offsets[n_points] && (!origin_shot || !origin_xy)) { set_last_error("null origin arrays"); return SFMX_EINVAL; }
+    }
+    if (n_candidates == 0) { g_count_ms = 0.f; return SFMX_OK; }   // nothing to write
+    DeviceCall F(stream, !inputs_on_device);
+    const hipStream_t st = F.st;
+    {
+        const int orc = F.open(g_count_slot, device);
+        if (orc != SFMX_OK) return orc;
+    }
+    Slot* const S = F.S;
+    int rc = SFMX_OK;
+    {
+        struct Entry { int32_t other, cand, pair; };
+        std::vector<int64_t> hoff(n_pairs + 1, 0);
+        std::vector<Entry> ent;
+        int64_t n_origins = 0, items = 0, slots = 0, nk = 0, n_matches = 0;
+        size_t n_used = 0;
+        if (inputs_on_device) {
+            if (n_pairs) SFMX_HIP_CHK(hipMemcpyAsync(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipMemcpyAsync(&n_origins, origin_offsets + n_points, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
+        } else {
+            if (n_pairs) std::memcpy(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1));
+            n_origins = origin_offsets[n_points];
+        }
+        if (hoff[0] != 0) { set_last_error("pair offsets do not start at 0"); rc = SFMX_EINVAL; goto done; }
+        for (int p = 0; p < n_pairs; ++p)
+            if (hoff[p + 1] < hoff[p]) { set_last_error("pair offsets not ascending"); rc = SFMX_EINVAL; goto done; }
+        n_matches = hoff[n_pairs];
+        if (n_origins < 0 || (n_origins + 255) / 256 > INT32_MAX) { set_last_error("origin record count out of range"); rc = SFMX_EINVAL; goto done; }
+        if (n_matches && !matches) { set_last_error("null argument"); rc = SFMX_EINVAL; goto done; }
+        // per (origin shot o, candidate s): the first visible pair in list order joining {s, o} (Scene.cpp:389-394)
+        for (int p = 0; p < n_pairs; ++p) {
+            const int L = pairs[2 * p], R = pairs[2 * p + 1];
+            if (L == R || (pair_active && !pair_active[p])) continue;
+            if (cand_of_shot[L] >= 0) ent.push_back(Entry{R, cand_of_shot[L], p});
+            if (cand_of_shot[R] >= 0) ent.push_back(Entry{L, cand_of_shot[R], p});
+        }
+        std::stable_sort(ent.begin(), ent.end(), [](const Entry& a, const Entry& b) {
+            return a.other != b.other ? a.other < b.other : a.cand < b.cand;
+        });
+        for (size_t i = ent.size(); i-- > 1;)   // only the first of every (o, s) run counts
+            if (ent[i].other == ent[i - 1].other && ent[i].cand == ent[i - 1].cand) ent[i].pair = -1;
+        for (size_t i = 0; i < ent.size(); ++i) {   // a first pair without matches has no table: no match through it
+            const int p = ent[i].pair;
+            if (p < 0) continue;
+            const int64_t m = hoff[p + 1] - hoff[p];
+            if (m <= 0) { ent[i].pair = -1; continue; }
+            if (!inputs_on_device) {   // host validation of the keypoint indices of the pairs that are read
+                const int L = pairs[2 * p], R = pairs[2 * p + 1];
+                for (int64_t k = hoff[p]; k < hoff[p + 1]; ++k)
+                    if (matches[k].queryIdx < 0 || matches[k].queryIdx >= n_keypoints[L] || matches[k].trainIdx < 0 ||
+                        matches[k].trainIdx >= n_keypoints[R]) {
+                        set_last_error("match index outside its image's keypoints");
+                        rc = SFMX_EINVAL;
+                        goto done;
+                    }
+            }
+            if (m > ((int64_t)1 << 29)) { set_last_error("a match list beyond 2^29 entries"); rc = SFMX_ECAPACITY; goto done; }   // its table's capacity is an int32
+            ++n_used;
+            items += m;
+        }
+        if (items >= INT32_MAX || n_used >= (size_t)INT32_MAX) { set_last_error("too many matches"); rc = SFMX_ECAPACITY; goto done; }
+        if (!inputs_on_device)
+            for (int i = 0; i < n_shots; ++i) nk += n_keypoints[i];
+        {
+            // device block: [tables of the call | hash tables | (host inputs: keypoints, matches, offsets, origins, counts)]
+            const bool H = F.host;
+            BlockLayout L;
+            UsedPair* usd;
+            int32_t *ufd, *tfd, *nkd, *ncd, *prd, *tv, *sd, *cd;
+            const float2** kpd;
+            unsigned long long* tk;
+            float2* kd;
+            sfmx_dmatch* md;
+            int64_t* od;
+            double* xd;
+            L.want(usd, n_used);
+            L.want(ufd, n_used);
+            L.want(tfd, (size_t)n_shots + 1);
+            L.want(nkd, n_shots);
+            L.want(ncd, n_candidates);
+            L.want(prd, 2 * (size_t)n_pairs);
+            L.want(kpd, n_shots);
+            const size_t b_tab = L.need;   // up to here: staged in pinned memory, one upload
+            for (const Entry& en : ent) {
+                if (en.pair < 0) continue;
+                const int64_t m = hoff[en.pair + 1] - hoff[en.pair];
+                int64_t cap = 16;
+                while (cap < 2 * m) cap <<= 1;
+                slots += cap;
+            }
+            L.want(tk, slots);
+            L.want(tv, slots);
+            L.want(kd, nk, H);
+            L.want(md, n_matches, H);
+            L.want(od, (size_t)n_pairs + 1, H);
+            L.want(sd, n_origins, H);
+            L.want(xd, 2 * (size_t)n_origins, H);
+            L.want(cd, n_candidates, H);
+            rc = F.reserve(L, b_tab);
+            if (rc != SFMX_OK) goto done;
+            UsedPair* hu = F.pinned(usd);
+            int32_t *huf = F.pinned(ufd), *htf = F.pinned(tfd);
+            size_t u = 0;
+            int64_t it = 0, sl = 0;
+            for (int o = 0; o <= n_shots; ++o) htf[o] = 0;
+            for (const Entry& en : ent) {
+                if (en.pair < 0) continue;
+                const int64_t m = hoff[en.pair + 1] - hoff[en.pair];
+                int64_t cap = 16;
+                while (cap < 2 * m) cap <<= 1;
+                hu[u] = UsedPair{en.pair, pairs[2 * en.pair] == en.other ? 1 : 0, sl, (int32_t)cap, en.cand};
+                huf[u] = (int32_t)it;
+                ++htf[en.other + 1];
+                ++u;
+                it += m;
+                sl += cap;
+            }
+            for (int o = 0; o < n_shots; ++o) htf[o + 1] += htf[o];
+            std::memcpy(F.pinned(nkd), n_keypoints, sizeof(int32_t) * n_shots);
+            for (int c = 0; c < n_candidates; ++c) F.pinned(ncd)[c] = n_keypoints[candidates[c]];
+            if (n_pairs) std::memcpy(F.pinned(prd), pairs, sizeof(int32_t) * 2 * n_pairs);
+            const float2** hk = F.pinned(kpd);
+            int64_t o = 0;
+            for (int i = 0; i < n_shots; ++i) {
+                if (H) {
+                    if (n_keypoints[i]) SFMX_HIP_CHK(hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st));
+                    hk[i] = kd + o;
+                    o += n_keypoints[i];
+                } else {
+                    hk[i] = reinterpret_cast<const float2*>(keypoints[i]);
+                }
+            }
+            SFMX_HIP_CHK(F.upload(b_tab));
+            const DMatchDev* dm = reinterpret_cast<const DMatchDev*>(n_matches ? F.in(matches, md, n_matches) : matches);
+            const int64_t* doff = n_pairs ? F.in(pair_offsets, od, (size_t)n_pairs + 1) : pair_offsets;
+            const int32_t* dshot = n_origins ? F.in(origin_shot, sd, n_origins) : origin_shot;
+            const double* dxy = n_origins ? F.in(origin_xy, xd, 2 * (size_t)n_origins) : origin_xy;
+            SFMX_HIP_CHK(F.err);
+            int32_t* dcount = F.out(out_count, cd);
+            (void)hipEventRecord(S->e0, st);
+            SFMX_HIP_CHK(hipMemsetAsync(dcount, 0, sizeof(int32_t) * n_candidates, st));
+            if (slots) {
+                SFMX_HIP_CHK(hipMemsetAsync(tk, 0xff, sizeof(unsigned long long) * slots, st));
+                SFMX_HIP_CHK(hipMemsetAsync(tv, 0x7f, sizeof(int32_t) * slots, st));
+            }
+            if (items)
+                build_tables_kernel<<<(unsigned)((items + 255) / 256), 256, 0, st>>>(usd, ufd, (int)n_used, items, doff, dm, kpd,
+                                                                                    nkd, prd, tk, tv);
+            if (items && n_origins)
+                count_kernel<<<(unsigned)((n_origins + 255) / 256), 256, 0, st>>>(n_origins, dshot, dxy, n_shots, tfd, usd, tk, tv,
+                                                                                doff, dm, ncd, n_candidates, dcount);
+            (void)hipEventRecord(S->e1, st);
+            SFMX_HIP_CHK(hipGetLastError());
+            SFMX_HIP_CHK(F.back(out_count, cd, n_candidates));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
+            float ms = -1.f;
+            (void)hipEventElapsedTime(&ms, S->e0, S->e1);
+            g_count_ms = ms;
+        }
+    done:;
+        rc = F.finish(rc, "sfmx_count_3d2d_matches");
+    }
     return rc;
 }
 

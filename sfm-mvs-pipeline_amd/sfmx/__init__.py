@@ -11,7 +11,7 @@ from .matching import (  # noqa: F401
     GridFeatureMatchingStrategy, calculate_shot_matches, match_pairs, pairs_unordered, pairs_video, pairs_grid,
 )
 
-from . import homography, scene, mvs, features, triangulate, pose, pnp, cloud, report  # noqa: F401,E402
+from . import homography, scene, mvs, features, triangulate, pose, pnp, cloud, report, sfm  # noqa: F401,E402
 from .report import (  # noqa: F401,E402
     reprojection_errors, reprojection_errors_device, colorize_pointcloud, colorize_pointcloud_device,
     writeToReprojectionErrorStatisticsCSV, writeToReprojectionErrorHistogramCSV, colorizePointcloud, writeToPLY,

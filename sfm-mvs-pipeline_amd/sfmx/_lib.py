@@ -99,9 +99,55 @@ class sfmx_cli_config(C.Structure):
                [("out", C.c_char * 1024)]
 
 
+class sfmx_sfm_params(C.Structure):
+    """include/sfmx_sfm.h"""
+    _fields_ = [("min_match_count_for_baseline", C.c_int32), ("_reserved", C.c_int32)] + \
+               [(n, C.c_double) for n in ("ransac_baseline_threshold", "ransac_pose_threshold",
+                                          "min_homography_inlier_ratio", "min_pose_inlier_ratio",
+                                          "max_reprojection_error", "point_merge_distance", "feature_merge_distance")]
+
+
+SFM_RELATIVE_POSE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int32))
+SFM_TRIANGULATE_PAIR_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32))
+SFM_ADD_ELEMENTS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_int32)
+SFM_COUNT_CANDIDATES_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32))
+SFM_REGISTER_SHOT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32,
+                                   C.POINTER(C.c_int32))
+SFM_ACCEPT_SHOT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32)
+SFM_BUNDLE_ADJUST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+
+
+class sfmx_sfm_steps(C.Structure):
+    _fields_ = [("relative_pose", SFM_RELATIVE_POSE_FN), ("triangulate_pair", SFM_TRIANGULATE_PAIR_FN),
+                ("add_elements", SFM_ADD_ELEMENTS_FN), ("count_candidates", SFM_COUNT_CANDIDATES_FN),
+                ("register_shot", SFM_REGISTER_SHOT_FN), ("accept_shot", SFM_ACCEPT_SHOT_FN),
+                ("bundle_adjust", SFM_BUNDLE_ADJUST_FN)]
+
+
+class sfmx_sfm_event(C.Structure):
+    _fields_ = [("event", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("_pad", C.c_int32), ("value", C.c_double)]
+
+
+SFM_N_STEPS = 7
+
+
+class sfmx_sfm_summary(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("ba_calls", "ba_iterations", "last_termination_type", "shots_recovered",
+                                         "pairs_triangulated", "pairs_failed", "pairs_open", "initial_pair")] + \
+               [("step_calls", C.c_int64 * SFM_N_STEPS), ("step_wall_ms", C.c_double * SFM_N_STEPS)]
+
+
+SFM_N_ROWS = 8
+
+
+class sfmx_sfm_timing(C.Structure):
+    _fields_ = [("calls", C.c_int64 * SFM_N_ROWS), ("device_ms", C.c_double * SFM_N_ROWS),
+                ("wall_ms", C.c_double * SFM_N_ROWS), ("handoff_bytes", C.c_int64 * SFM_N_ROWS)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p)
 
-# Every symbol include/sfmx.h (and include/sfmx_ba.h, sfmx_homography.h, sfmx_triangulate.h, sfmx_pose.h, sfmx_pnp.h, sfmx_scene.h, sfmx_cloud.h, sfmx_report.h) declares, with its ctypes prototype.
+# Every symbol include/sfmx.h (and include/sfmx_ba.h, sfmx_homography.h, sfmx_triangulate.h, sfmx_pose.h, sfmx_pnp.h, sfmx_scene.h, sfmx_sfm.h, sfmx_cloud.h, sfmx_report.h) declares, with its ctypes prototype.
 _P = C.POINTER
 _i32p, _i64p, _vp = _P(C.c_int32), _P(C.c_int64), C.c_void_p
 PROTOTYPES = {
@@ -171,8 +217,21 @@ PROTOTYPES = {
     "sfmx_find_3d2d_matches": (C.c_int, [_P(_vp), _i32p, C.c_int32, _i32p, C.c_int32, _vp, _vp, _vp, C.c_int32,
                                          _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "sfmx_find_3d2d_last_kernel_ms": (C.c_float, []),
+    "sfmx_count_3d2d_matches": (C.c_int, [_P(_vp), _i32p, C.c_int32, _i32p, C.c_int32, _i32p, _vp, _vp, _vp, C.c_int32,
+                                          _vp, _vp, _i32p, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "sfmx_count_3d2d_last_kernel_ms": (C.c_float, []),
     "sfmx_ba_observations_from_origins": (C.c_int, [_i64p, C.c_int32, _i32p, _P(C.c_double), C.c_int32, _i32p, _i32p,
                                                     _P(C.c_double), _i32p, _i32p, _i32p]),
+    # include/sfmx_sfm.h
+    "sfmx_sfm_default_params": (C.c_int, [_P(sfmx_sfm_params)]),
+    "sfmx_sfm_triangulate_steps": (C.c_int, [_P(sfmx_sfm_steps), _vp, _P(sfmx_sfm_params), C.c_int32, _i32p, C.c_int32,
+                                             _i32p, _P(C.c_double), _i32p, _i32p, _i32p, _P(sfmx_sfm_event), C.c_int64,
+                                             _i64p, _P(sfmx_sfm_summary)]),
+    "sfmx_sfm_triangulate": (C.c_int, [_P(_vp), _i32p, C.c_int32, _i32p, _P(sfmx_tri_camera), C.c_int32, C.c_int32, _i32p,
+                                       C.c_int32, _vp, _i64p, _P(C.c_double), _P(sfmx_sfm_params), C.c_int32, _i32p,
+                                       _P(C.c_double), _P(sfmx_tri_camera), _vp, C.c_int64, _i64p, _i32p, _vp, C.c_int64,
+                                       _i64p, _i64p, _vp, _i64p, _i32p, _P(sfmx_sfm_event), C.c_int64, _i64p,
+                                       _P(sfmx_sfm_summary), _P(sfmx_sfm_timing)]),
     "sfmx_merge_pointcloud_3d2d": (C.c_int, [_P(_vp), _i32p, C.c_int32, _i32p, C.c_int32, _vp, _vp,
                                              _vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp,
                                              C.c_double, C.c_double, C.c_int32, C.c_int32, _vp,

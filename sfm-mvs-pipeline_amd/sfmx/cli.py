@@ -14,10 +14,18 @@ run-scripts' flag sets unchanged and drives the sfmx hot path with them:
 
 Parsing and the flag -> configuration mapping (defaults, warnings, the SfM setters'
 validation) are native: include/sfmx_cli.h, csrc/cli.cpp.  This module is the host
-driver around them.  Stages after the match graph that sfmx does not accelerate
-(incremental registration / triangulation, MVS densify, mesh; SURVEY.md §8 marks
-them out of scope) are reported and skipped; ``--sfmx-plan`` (an sfmx-only flag)
-prints the resolved plan and stops before any device work.
+driver around them.  ``--sfmx-plan`` (an sfmx-only flag) prints the resolved plan and
+stops before any device work.  ``--sfmx-reconstruct`` (an sfmx-only flag) goes on after
+the match graph:
+
+    triangulate         SfM::triangulate (SfM.cpp:164-381) over the GPU rows (sfmx.sfm.triangulate)
+                        with the -P thresholds (PhotogrammetrieCli.cpp:96-111)
+    scene outputs       cameras_recovered.ply, pointcloud_sparse.ply (coloured from the images with
+                        --colored), with --stats reprojectionerror.stat.csv / .hist.csv
+                        (PhotogrammetrieCli.cpp:115-132), a `reconstruction` object in sfmx_pipeline.json
+
+Without it the run ends at the match graph, as before.  MVS densify and mesh
+(--dense, --mesh; SURVEY.md §8 marks them out of scope) are reported and skipped.
 
 ``Photogrammetrie -Prun=pcl-stats -Pinput=cloud.ply -Pstats=... -Pneighbors=... -Pquality=...`` is the
 second sub-program (PclStatsCli.cpp): the neighbour search of sfmx.cloud on the GPU, then the three files.
@@ -35,7 +43,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from ._lib import lib, check, sfmx_cli_config
+from ._lib import lib, check, sfmx_cli_config, SfmxError
 
 RUN_HELP, RUN_PHOTOGRAMMETRIE, RUN_PCL_STATS = 0, 1, 2
 DETECTOR_SIFT, DETECTOR_ORB = 0, 1
@@ -45,6 +53,7 @@ LOG_TRACE, LOG_DEBUG, LOG_INFO, LOG_WARN, LOG_ERROR = 0, 1, 2, 3, 4
 CAMERA_MODELS = {1: "Simple", 3: "SimpleRadial", 7: "Distortion"}
 STRATEGY_NAMES = {STRATEGY_UNORDERED: "Unordered", STRATEGY_VIDEO: "Video", STRATEGY_GRID: "Grid"}
 EXIT_USAGE = 255          # the reference's exit(-1)
+EXIT_FAILURE = 1          # a device or internal error of the library (sfmx only; the reference aborts on an exception)
 
 
 
@@ -231,7 +240,69 @@ def load_gray(path: str, resolution=None) -> np.ndarray:
     return np.ascontiguousarray(g)
 
 
+def load_color(path: str, resolution=None) -> np.ndarray:
+    """cv::imread(path, IMREAD_COLOR): h x w x 3 uint8, BGR (+ the resize of load_gray).  Decoder builds differ
+    as for load_gray."""
+    from PIL import Image, ImageOps
+    with Image.open(path) as im:
+        im = ImageOps.exif_transpose(im).convert("RGB")
+        if resolution is not None and im.size != tuple(resolution):
+            im = im.resize(tuple(resolution), Image.BILINEAR)
+        rgb = np.asarray(im, np.uint8)
+    return np.ascontiguousarray(rgb[..., ::-1])
+
+
 # ---- the photogrammetrie sub-program --------------------------------------------
+
+def sfm_params(cfg):
+    """The SfM setters of PhotogrammetrieCli.cpp:96-111 as sfmx_sfm_params."""
+    from . import sfm
+    return sfm.default_params(min_match_count_for_baseline=cfg.baseline_homography_threshold,
+                              ransac_baseline_threshold=cfg.ransac_baseline_threshold,
+                              ransac_pose_threshold=cfg.ransac_pose_threshold,
+                              min_homography_inlier_ratio=cfg.homography_inlier_ratio_threshold,
+                              min_pose_inlier_ratio=cfg.pose_inlier_ratio_threshold,
+                              max_reprojection_error=cfg.reprojection_error_threshold,
+                              point_merge_distance=cfg.pointcloud_point_merge_distance,
+                              feature_merge_distance=cfg.pointcloud_feature_merge_distance)
+
+
+def initial_camera(camera: dict):
+    """(K, dist) of the plan's camera: f = 1.2 * max(w, h), the centre, no distortion (PhotogrammetrieCli.cpp:296-314)."""
+    f = camera["focal_length"]
+    return np.array([[f, 0, camera["cx"]], [0, f, camera["cy"]], [0, 0, 1.0]]), np.zeros(5)
+
+
+def reconstruction_object(r: dict) -> dict:
+    """What sfmx_pipeline.json keeps of a sfmx.sfm.triangulate result (nothing that changes from run to run)."""
+    s = r["summary"]
+    return {"recovered_shots": [int(i) for i in np.flatnonzero(r["recovered"])], "points": int(len(r["xyz"])),
+            "records": int(len(r["origin_shot"])), "pair_state": [int(v) for v in r["pair_state"]],
+            "match_counts": [int(v) for v in np.diff(r["offsets"])],
+            "camera": {"K": r["camera"][0].reshape(-1).tolist(), "distortion": r["camera"][1].tolist()},
+            "trace": [list(e) for e in r["trace"]],
+            "summary": {k: v for k, v in s.items() if k != "step_wall_ms"}}
+
+
+def write_scene_outputs(workdir, r: dict, resolution, image_paths_, colored: bool, stats: bool) -> None:
+    """PhotogrammetrieCli.cpp:115-132 on a sfmx.sfm.triangulate result."""
+    from . import report
+    w, h = resolution
+    n = len(r["recovered"])
+    poses = np.where(np.isnan(r["poses"]), 0.0, r["poses"])
+    rgb = None
+    if colored:                                                    # scene.colorizePointcloud() (:116)
+        images = [load_color(p, (w, h)) for p in image_paths_]
+        rgb = report.colorizePointcloud(len(r["xyz"]), r["origin_offsets"], r["origin_shot"], r["origin_xy"], images)
+    report.writeToPLY(os.path.join(workdir, "cameras_recovered.ply"), cameras=[(w, h, r["camera"][0])],
+                      shots=[(0, bool(r["recovered"][i]), poses[i]) for i in range(n)])
+    report.writeToPLY(os.path.join(workdir, "pointcloud_sparse.ply"), r["xyz"], rgb)
+    if stats:                                                      # (:126-132)
+        err = report.reprojection_errors(r["xyz"], r["origin_offsets"], r["origin_shot"], r["origin_xy"], [r["camera"]],
+                                         np.zeros(n, np.int32), poses)
+        report.writeToReprojectionErrorStatisticsCSV(err, os.path.join(workdir, "reprojectionerror.stat.csv"))
+        report.writeToReprojectionErrorHistogramCSV(err, os.path.join(workdir, "reprojectionerror.hist.csv"))
+
 
 def strategy_pairs(cfg) -> "callable":
     from . import matching
@@ -278,6 +349,7 @@ class PhotogrammetrieCli:
                 log.log(m, lvl)
             return EXIT_USAGE
         plan_only = args.isFlag("sfmx-plan")
+        reconstruct = args.isFlag("sfmx-reconstruct")
 
         paths = image_paths(args.getArgs("image"), log)            # prepareScene (:249-318)
         log.debug(f"{len(paths)} images found")
@@ -344,6 +416,8 @@ class PhotogrammetrieCli:
                                    kpairs, kmatches, koff, cfg.ransac_matching_threshold)
         self._time("homography", t0)
 
+        if reconstruct:
+            return self._reconstruct(workdir, cfg, plan, paths, feats, kpairs, kmatches, koff, ratios, (w, h))
         self._write(workdir, cfg, plan, paths, feats, kpairs, kmatches, koff, ratios)
         skipped = [f for f in ("dense", "mesh", "sgm", "refine_mesh", "no_decimate", "colored") if getattr(cfg, f)]
         log.info("match graph done; registration / triangulation"
@@ -351,7 +425,37 @@ class PhotogrammetrieCli:
                  + " are outside the sfmx hot path and were not run (SURVEY.md §8)")
         return 0
 
-    def _write(self, workdir, cfg, plan, paths, feats, pairs, matches, off, ratios):
+    def _reconstruct(self, workdir, cfg, plan, paths, feats, pairs, matches, off, ratios, resolution) -> int:
+        """--sfmx-reconstruct: SfM::triangulate and the scene outputs (PhotogrammetrieCli.cpp:113-132)."""
+        from . import sfm
+        log = self.logger
+        t0 = time.perf_counter()
+        try:
+            r = sfm.triangulate([np.stack([k["x"], k["y"]], 1) for k, _ in feats], [resolution] * len(paths),
+                                initial_camera(plan["camera"]), cfg.camera_model, pairs, matches, off, ratios, sfm_params(cfg))
+        except ValueError as e:                                    # an argument the library refuses (a -P value)
+            log.error(f"reconstruction: {e}")
+            return EXIT_USAGE
+        except SfmxError as e:                                     # a device or internal error: not a usage error
+            log.error(f"reconstruction failed: {e}")
+            return EXIT_FAILURE
+        self._time("triangulate", t0)
+        if not r["recovered"].any():
+            log.warn("no initial pair could be triangulated")      # SfM.cpp:240
+        log.info(f"reconstruction done: {int(r['recovered'].sum())} of {len(paths)} shots recovered, {len(r['xyz'])} points, "
+                 f"{r['summary']['pairs_triangulated']} pairs triangulated, {r['summary']['pairs_failed']} failed")
+        t0 = time.perf_counter()
+        write_scene_outputs(workdir, r, resolution, paths, bool(cfg.colored), bool(cfg.stats))
+        self._time("scene_outputs", t0)
+        self._write(workdir, cfg, plan, paths, feats, pairs, matches, off, ratios,
+                    extra={"reconstruction": reconstruction_object(r), "reconstruction_timing": r["timing"]})
+        skipped = [f for f in ("dense", "mesh", "sgm", "refine_mesh", "no_decimate") if getattr(cfg, f)]
+        if skipped:
+            log.info(", ".join("--" + s.replace("_", "-") for s in skipped)
+                     + " are outside the sfmx hot path and were not run (SURVEY.md §8)")
+        return 0
+
+    def _write(self, workdir, cfg, plan, paths, feats, pairs, matches, off, ratios, extra=None):
         with open(os.path.join(workdir, "shot_matches.csv"), "w") as f:
             f.write("left,right,left_image,right_image,matches,homography_inlier_ratio\n")
             for p, (l, r) in enumerate(pairs):
@@ -359,7 +463,7 @@ class PhotogrammetrieCli:
                         f"{int(off[p + 1] - off[p])},{ratios[p]!r}\n")
         summary = dict(plan, n_features=[int(len(k)) for k, _ in feats], kept_pairs=pairs.tolist(),
                        match_counts=[int(off[p + 1] - off[p]) for p in range(len(pairs))],
-                       homography_inlier_ratios=[float(r) for r in ratios], timings_ms=self.timings)
+                       homography_inlier_ratios=[float(r) for r in ratios], timings_ms=self.timings, **(extra or {}))
         with open(os.path.join(workdir, "sfmx_pipeline.json"), "w") as f:
             json.dump(summary, f, indent=1)
         if cfg.stats:                                              # --stats (:126-132)

@@ -67,6 +67,60 @@ def last_kernel_ms() -> float:
     return float(lib.sfmx_find_3d2d_last_kernel_ms())
 
 
+def count_3d2d_matches(keypoints: Sequence[np.ndarray], pairs, matches, offsets, origin_offsets, origin_shot,
+                       origin_xy, candidates, pair_active=None, device: int = 0, stream: int = 0) -> np.ndarray:
+    """The candidate ranking of SfM::triangulate (SfM.cpp:276-300) in one call: -> int32 per candidate shot,
+    the number of origin records ``find_3d2d_matches(shot=candidate)`` matches over the pairs that
+    `pair_active` (None: all) leaves visible."""
+    kps = [np.ascontiguousarray(k, np.float32).reshape(-1, 2) for k in keypoints]
+    nkp = np.array([len(k) for k in kps], np.int32)
+    ptrs = (C.c_void_p * max(len(kps), 1))(*[k.ctypes.data for k in kps])
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    act = None if pair_active is None else np.ascontiguousarray(pair_active, np.int32)
+    if act is not None and len(act) != len(pairs):
+        raise ValueError("pair_active must have one entry per pair")
+    m = np.ascontiguousarray(matches, DMATCH_DTYPE)
+    off = np.ascontiguousarray(offsets, np.int64)
+    if len(off) != len(pairs) + 1:
+        raise ValueError("offsets must have n_pairs + 1 entries")
+    oo = np.ascontiguousarray(origin_offsets, np.int64)
+    os_ = np.ascontiguousarray(origin_shot, np.int32)
+    oxy = np.ascontiguousarray(origin_xy, np.float64).reshape(-1, 2)
+    cand = np.ascontiguousarray(candidates, np.int32).reshape(-1)
+    if len(oo) < 1 or len(os_) != len(oxy) or int(oo[-1]) > len(os_):
+        raise ValueError("origin arrays shorter than their offsets")
+    n = int(oo[-1])
+    out = np.zeros(max(len(cand), 1), np.int32)
+    check(lib.sfmx_count_3d2d_matches(ptrs, _p(nkp, C.c_int32), len(kps), _p(pairs, C.c_int32), len(pairs),
+                                      None if act is None else _p(act, C.c_int32), m.ctypes.data if len(m) else None,
+                                      off.ctypes.data, oo.ctypes.data, len(oo) - 1, os_.ctypes.data if n > 0 else None,
+                                      oxy.ctypes.data if n > 0 else None, _p(cand, C.c_int32), len(cand), 0, int(device),
+                                      stream or None, out.ctypes.data), "sfmx_count_3d2d_matches")
+    return out[:len(cand)]
+
+
+def count_3d2d_matches_device(keypoint_ptrs, n_keypoints, pairs, matches_ptr, offsets_ptr, origin_offsets_ptr, n_points,
+                              origin_shot_ptr, origin_xy_ptr, candidates, out_count_ptr, pair_active=None,
+                              device: int = 0, stream: int = 0):
+    """Same with every array resident on `device` (pairs, pair_active and candidates stay host)."""
+    nkp = np.ascontiguousarray(n_keypoints, np.int32)
+    ptrs = (C.c_void_p * max(len(nkp), 1))(*keypoint_ptrs)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    act = None if pair_active is None else np.ascontiguousarray(pair_active, np.int32)
+    if act is not None and len(act) != len(pairs):
+        raise ValueError("pair_active must have one entry per pair")
+    cand = np.ascontiguousarray(candidates, np.int32).reshape(-1)
+    check(lib.sfmx_count_3d2d_matches(ptrs, _p(nkp, C.c_int32), len(nkp), _p(pairs, C.c_int32), len(pairs),
+                                      None if act is None else _p(act, C.c_int32), matches_ptr or None, offsets_ptr,
+                                      origin_offsets_ptr, int(n_points), origin_shot_ptr or None, origin_xy_ptr or None,
+                                      _p(cand, C.c_int32), len(cand), 1, int(device), stream or None,
+                                      out_count_ptr or None), "sfmx_count_3d2d_matches")
+
+
+def count_last_kernel_ms() -> float:
+    return float(lib.sfmx_count_3d2d_last_kernel_ms())
+
+
 def ba_observations_from_origins(origin_offsets, origin_shot, origin_xy, n_shots: int):
     """-> dict(obs_point, obs_cam, obs_xy, pose_of_shot, shot_of_pose): the
     sfmx_ba_problem observation arrays in AddResidualBlock order
