@@ -37,8 +37,17 @@ extern "C" {
  * The reference appends matches under `omp critical` in a nondeterministic
  * order; here they are reported per origin record (point-major), which keys
  * parity by (point, origin).
+ * SFMX_EINVAL: `shot` or a pair shot outside [0, n_shots), a negative keypoint count,
+ * pair offsets that do not ascend from 0, an origin record count that is negative or
+ * beyond 2^39, matches NULL with a non-empty list, (host) a match index outside its
+ * image's keypoints in a pair that is read (the pairs and checks of
+ * sfmx_count_3d2d_matches for the one candidate `shot`), 2^31 matches or more in the
+ * pairs that are read or one list of more than 2^29.
+ * The device block of a call is kept for the next one; calls of this function and of
+ * sfmx_count_3d2d_matches on one device take turns.
  * inputs_on_device = 1: keypoints[i], matches, pair_offsets, origin_* and the
- * out_* arrays are device pointers on `device`; 0: host memory. */
+ * out_* arrays are device pointers on `device`; pairs is host memory always;
+ * 0: host memory. */
 int sfmx_find_3d2d_matches(const sfmx_point2f* const* keypoints, const int32_t* n_keypoints, int32_t n_shots,
                            const int32_t* pairs, int32_t n_pairs, const sfmx_dmatch* matches,
                            const int64_t* pair_offsets, const int64_t* origin_offsets, int32_t n_points,

@@ -1,6 +1,8 @@
-// The host-side call frame of the geometry rows (homography, triangulate, pose, pnp, cloud): a per-device slot
-// kept between calls, the layout of its device block, the staging of host arguments, one error macro, one tail.
-// A row writes its validation, its host tables and its launches; everything around them is here.
+// The host-side call frame of the geometry rows (homography, triangulate, pose, pnp, cloud, report, scene, merge):
+// a per-device slot kept between calls, the layout of its device block, the staging of host arguments, one error
+// macro, one tail.  A row writes its validation, its host tables and its launches; everything around them is here.
+// A block whose size is known only in mid-call (merge's link list) is a second slot array and a second DeviceCall
+// on the same device and stream, always opened after the first.
 //
 //     DeviceCall F(stream, host_inputs);
 //     if (<the call needs a device>) { const int orc = F.open(g_slot, device); if (orc != SFMX_OK) return orc; }

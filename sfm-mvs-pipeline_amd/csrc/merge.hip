@@ -41,7 +41,9 @@
 #include <vector>
 
 #include "../../include/sfmx_scene.h"
+#include "device_call.hpp"
 #include "match_common.hpp"
+#include "scene_plan.hpp"
 
 namespace sfmx {
 namespace merge {
@@ -255,65 +257,14 @@ void scatter_kernel(int64_t n_crec, int64_t n_nrec, int n_cloud, int n_out, cons
 
 thread_local float g_last_ms = -1.f;
 thread_local int64_t g_last_stats[3] = {0, 0, 0};   // merges decided statically, dynamically; new-new links
-
-struct Bufs {               // device work buffers: the requests of a call are served by one allocation
-    struct Request { void** where; size_t bytes; };
-    std::vector<void*> ptrs;
-    std::vector<Request> requests;
-    ~Bufs() { for (void* q : ptrs) (void)hipFree(q); }
-    void* alloc(size_t bytes) {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
-        ptrs.push_back(q);
-        return q;
-    }
-    template <class T> void want(T*& p, int64_t n) {   // p is set by commit()
-        p = nullptr;
-        requests.push_back({reinterpret_cast<void**>(&p), (sizeof(T) * (size_t)std::max<int64_t>(n, 1) + 255) & ~(size_t)255});
-    }
-    bool commit() {
-        size_t total = 0;
-        for (const Request& r : requests) total += r.bytes;
-        char* q = static_cast<char*>(alloc(total));
-        if (!q) return false;
-        for (const Request& r : requests) { *r.where = q; q += r.bytes; }
-        requests.clear();
-        return true;
-    }
-};
-
-struct SyncOnExit {        // declared after the host buffers of the async copies: the stream drains before they go
-    hipStream_t st;
-    const bool* armed;     // the device was selected (a host-only call touches no device)
-    ~SyncOnExit() { if (*armed) (void)hipStreamSynchronize(st); }
-};
-
-struct Events {            // the three timed spans of a call
-    hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-
-static uint32_t capacity_for(int64_t entries) {   // power of two, load factor <= 1/2
-    uint32_t cap = 16;
-    while ((int64_t)cap < 2 * entries) cap <<= 1;
-    return cap;
-}
-
-static bool offsets_ok(const int64_t* off, int32_t n) {
-    if (off[0] != 0) return false;
-    for (int32_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return false;
-    return true;
-}
+Slot g_slot[64];        // csrc/device_call.hpp: the block of a call
+Slot g_link_slot[64];   // the link list, whose length only the first probe gives: a block of its own, taken after g_slot's
 
 }  // namespace merge
 }  // namespace sfmx
 
 using namespace sfmx;
 using namespace sfmx::merge;
-
-#define MCHK(expr) do { if ((expr) != hipSuccess) { rc = SFMX_EDEVICE; set_last_error("HIP error in " #expr); goto done; } } while (0)
-#define MFAIL(code, msg) do { rc = (code); set_last_error(msg); goto done; } while (0)
 
 extern "C" {
 
@@ -349,85 +300,89 @@ int sfmx_merge_pointcloud_3d2d(const sfmx_point2f* const* keypoints, const int32
         set_last_error("null argument");
         return SFMX_EINVAL;
     }
-    for (int p = 0; p < n_pairs; ++p)
-        if (pairs[2 * p] < 0 || pairs[2 * p] >= n_shots || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= n_shots) {
-            set_last_error("pair shot index out of range");
-            return SFMX_EINVAL;
-        }
-    const hipStream_t st = (hipStream_t)stream;
+    if (!plan::shots_in_range(pairs, n_pairs, n_shots)) { set_last_error("pair shot index out of range"); return SFMX_EINVAL; }
     const double D = point_merge_distance, F = feature_merge_distance;
-    int prev = -1;
-    bool device_set = false;
+    DeviceCall call(stream, !inputs_on_device);   // opened where a device is first needed: a host call with nothing new opens none
+    DeviceCall link_call(stream, false);          // the link list's block
+    const hipStream_t st = call.st;
+    const bool H = call.host;
     int rc = SFMX_OK;
     try {
-        Bufs b;
         // host copies of what the host resolution reads (staged from the device when inputs_on_device)
         std::vector<int64_t> hoff(n_pairs + 1, 0), hco(n_cloud + 1, 0), hno(n_new + 1, 0);
         std::vector<int32_t> hcs, hns;
         std::vector<double> hcxy, hnxy, hcx, hnx;
+        // and of what comes back from the kernels or goes up to them; all alive until the frame's tail has drained the stream
+        std::vector<Summary> hs;
+        std::vector<int32_t> hcount, hlist, htarget, happ;
+        std::vector<int64_t> hloff, hdest, hout;
+        std::vector<double> hdist;
+        int32_t hfull = 0;
         const int64_t *co = cloud_origin_offsets, *no = new_origin_offsets;
         const int32_t *cs = cloud_origin_shot, *ns = new_origin_shot;
         const double *cxy = cloud_origin_xy, *nxy = new_origin_xy, *cx = cloud_xyz, *nx = new_xyz;
         int64_t n_crec = 0, n_nrec = 0, n_matches = 0;
-        const SyncOnExit drain_staging{st, &device_set};
-        if (inputs_on_device) {
-            int ndev = 0;
-            if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) MFAIL(SFMX_EDEVICE, "no HIP device visible");
-            if (device < 0 || device >= ndev) MFAIL(SFMX_EINVAL, "device index out of range");
-            (void)hipGetDevice(&prev);
-            if (hipSetDevice(device) != hipSuccess) MFAIL(SFMX_EDEVICE, "cannot select the device");
-            device_set = true;
-            if (n_pairs) MCHK(hipMemcpyAsync(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
-            MCHK(hipMemcpyAsync(hco.data(), cloud_origin_offsets, sizeof(int64_t) * (n_cloud + 1), hipMemcpyDeviceToHost, st));
-            MCHK(hipMemcpyAsync(hno.data(), new_origin_offsets, sizeof(int64_t) * (n_new + 1), hipMemcpyDeviceToHost, st));
-            MCHK(hipStreamSynchronize(st));
+        if (!H) {
+            const int orc = call.open(g_slot, device);
+            if (orc != SFMX_OK) return orc;
+            if (n_pairs) SFMX_HIP_CHK(hipMemcpyAsync(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipMemcpyAsync(hco.data(), cloud_origin_offsets, sizeof(int64_t) * (n_cloud + 1), hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipMemcpyAsync(hno.data(), new_origin_offsets, sizeof(int64_t) * (n_new + 1), hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
             co = hco.data();
             no = hno.data();
         } else if (n_pairs) {
             std::memcpy(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1));
         }
-        if (!offsets_ok(hoff.data(), n_pairs)) MFAIL(SFMX_EINVAL, "pair offsets do not ascend from 0");
-        if (!offsets_ok(co, n_cloud)) MFAIL(SFMX_EINVAL, "cloud origin offsets do not ascend from 0");
-        if (!offsets_ok(no, n_new)) MFAIL(SFMX_EINVAL, "new origin offsets do not ascend from 0");
+        if (!plan::offsets_ascend(hoff.data(), n_pairs)) { set_last_error("pair offsets do not ascend from 0"); rc = SFMX_EINVAL; goto done; }
+        if (!plan::offsets_ascend(co, n_cloud)) { set_last_error("cloud origin offsets do not ascend from 0"); rc = SFMX_EINVAL; goto done; }
+        if (!plan::offsets_ascend(no, n_new)) { set_last_error("new origin offsets do not ascend from 0"); rc = SFMX_EINVAL; goto done; }
         n_crec = co[n_cloud];
         n_nrec = no[n_new];
         n_matches = hoff[n_pairs];
         // table capacities (2 x entries, rounded up to a power of two) and entry indices stay within 32 bits
-        if (n_crec > (1 << 30) || n_nrec > (1 << 30) || n_matches > (1 << 29)) MFAIL(SFMX_ECAPACITY, "too many origin records or matches for one call");
+        if (n_crec > (1 << 30) || n_nrec > (1 << 30) || n_matches > (1 << 29)) {
+            set_last_error("too many origin records or matches for one call");
+            rc = SFMX_ECAPACITY;
+            goto done;
+        }
         if ((n_crec && (!cloud_origin_shot || !cloud_origin_xy)) || (n_nrec && (!new_origin_shot || !new_origin_xy)) ||
-            (n_crec + n_nrec && (!out_origin_shot || !out_origin_xy)) || (n_matches && !matches))
-            MFAIL(SFMX_EINVAL, "null argument");
-        if (inputs_on_device) {
+            (n_crec + n_nrec && (!out_origin_shot || !out_origin_xy)) || (n_matches && !matches)) {
+            set_last_error("null argument");
+            rc = SFMX_EINVAL;
+            goto done;
+        }
+        if (!H) {
             hcs.resize(n_crec); hcxy.resize(2 * n_crec); hcx.resize(3 * (size_t)n_cloud);
             hns.resize(n_nrec); hnxy.resize(2 * n_nrec); hnx.resize(3 * (size_t)n_new);
             if (n_crec) {
-                MCHK(hipMemcpyAsync(hcs.data(), cloud_origin_shot, sizeof(int32_t) * n_crec, hipMemcpyDeviceToHost, st));
-                MCHK(hipMemcpyAsync(hcxy.data(), cloud_origin_xy, sizeof(double) * 2 * n_crec, hipMemcpyDeviceToHost, st));
+                SFMX_HIP_CHK(hipMemcpyAsync(hcs.data(), cloud_origin_shot, sizeof(int32_t) * n_crec, hipMemcpyDeviceToHost, st));
+                SFMX_HIP_CHK(hipMemcpyAsync(hcxy.data(), cloud_origin_xy, sizeof(double) * 2 * n_crec, hipMemcpyDeviceToHost, st));
             }
             if (n_nrec) {
-                MCHK(hipMemcpyAsync(hns.data(), new_origin_shot, sizeof(int32_t) * n_nrec, hipMemcpyDeviceToHost, st));
-                MCHK(hipMemcpyAsync(hnxy.data(), new_origin_xy, sizeof(double) * 2 * n_nrec, hipMemcpyDeviceToHost, st));
+                SFMX_HIP_CHK(hipMemcpyAsync(hns.data(), new_origin_shot, sizeof(int32_t) * n_nrec, hipMemcpyDeviceToHost, st));
+                SFMX_HIP_CHK(hipMemcpyAsync(hnxy.data(), new_origin_xy, sizeof(double) * 2 * n_nrec, hipMemcpyDeviceToHost, st));
             }
-            if (n_cloud) MCHK(hipMemcpyAsync(hcx.data(), cloud_xyz, sizeof(double) * 3 * n_cloud, hipMemcpyDeviceToHost, st));
-            if (n_new) MCHK(hipMemcpyAsync(hnx.data(), new_xyz, sizeof(double) * 3 * n_new, hipMemcpyDeviceToHost, st));
-            MCHK(hipStreamSynchronize(st));
+            if (n_cloud) SFMX_HIP_CHK(hipMemcpyAsync(hcx.data(), cloud_xyz, sizeof(double) * 3 * n_cloud, hipMemcpyDeviceToHost, st));
+            if (n_new) SFMX_HIP_CHK(hipMemcpyAsync(hnx.data(), new_xyz, sizeof(double) * 3 * n_new, hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
             cs = hcs.data(); cxy = hcxy.data(); cx = hcx.data();
             ns = hns.data(); nxy = hnxy.data(); nx = hnx.data();
         }
         for (int64_t r = 0; r < n_crec; ++r)
-            if (cs[r] < 0 || cs[r] >= n_shots) MFAIL(SFMX_EINVAL, "cloud origin shot out of range");
+            if (cs[r] < 0 || cs[r] >= n_shots) { set_last_error("cloud origin shot out of range"); rc = SFMX_EINVAL; goto done; }
         for (int64_t r = 0; r < n_nrec; ++r)
-            if (ns[r] < 0 || ns[r] >= n_shots) MFAIL(SFMX_EINVAL, "new origin shot out of range");
+            if (ns[r] < 0 || ns[r] >= n_shots) { set_last_error("new origin shot out of range"); rc = SFMX_EINVAL; goto done; }
 
         if (n_new == 0) {   // nothing to merge: the cloud goes through unchanged, no kernel
-            if (inputs_on_device) {
-                if (n_cloud) MCHK(hipMemcpyAsync(out_xyz, cloud_xyz, sizeof(double) * 3 * n_cloud, hipMemcpyDeviceToDevice, st));
-                MCHK(hipMemcpyAsync(out_origin_offsets, cloud_origin_offsets, sizeof(int64_t) * (n_cloud + 1), hipMemcpyDeviceToDevice, st));
+            if (!H) {
+                if (n_cloud) SFMX_HIP_CHK(hipMemcpyAsync(out_xyz, cloud_xyz, sizeof(double) * 3 * n_cloud, hipMemcpyDeviceToDevice, st));
+                SFMX_HIP_CHK(hipMemcpyAsync(out_origin_offsets, cloud_origin_offsets, sizeof(int64_t) * (n_cloud + 1), hipMemcpyDeviceToDevice, st));
                 if (n_crec) {
-                    MCHK(hipMemcpyAsync(out_origin_shot, cloud_origin_shot, sizeof(int32_t) * n_crec, hipMemcpyDeviceToDevice, st));
-                    MCHK(hipMemcpyAsync(out_origin_xy, cloud_origin_xy, sizeof(double) * 2 * n_crec, hipMemcpyDeviceToDevice, st));
+                    SFMX_HIP_CHK(hipMemcpyAsync(out_origin_shot, cloud_origin_shot, sizeof(int32_t) * n_crec, hipMemcpyDeviceToDevice, st));
+                    SFMX_HIP_CHK(hipMemcpyAsync(out_origin_xy, cloud_origin_xy, sizeof(double) * 2 * n_crec, hipMemcpyDeviceToDevice, st));
                 }
-                MCHK(hipStreamSynchronize(st));
+                SFMX_HIP_CHK(hipStreamSynchronize(st));
             } else {
                 if (n_cloud) std::memcpy(out_xyz, cloud_xyz, sizeof(double) * 3 * n_cloud);
                 std::memcpy(out_origin_offsets, cloud_origin_offsets, sizeof(int64_t) * (n_cloud + 1));
@@ -443,153 +398,114 @@ int sfmx_merge_pointcloud_3d2d(const sfmx_point2f* const* keypoints, const int32
             goto done;
         }
 
-        if (!device_set) {
-            int ndev = 0;
-            if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) MFAIL(SFMX_EDEVICE, "no HIP device visible");
-            if (device < 0 || device >= ndev) MFAIL(SFMX_EINVAL, "device index out of range");
-            (void)hipGetDevice(&prev);
-            if (hipSetDevice(device) != hipSuccess) MFAIL(SFMX_EDEVICE, "cannot select the device");
-            device_set = true;
+        if (H) {
+            const int orc = call.open(g_slot, device);
+            if (orc != SFMX_OK) return orc;
         }
+        if (H && !plan::counts_non_negative(n_keypoints, n_shots)) { set_last_error("negative keypoint count"); rc = SFMX_EINVAL; goto done; }
         {
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-                MFAIL(SFMX_EDEVICE, "sfmx kernels are built for gfx950 only");
-        }
-        {
-            // 1. first pair per unordered shot pair (Scene.cpp:505-520: the loop breaks at the first pair
-            //    joining the two shots in either orientation); a pair of a shot with itself joins nothing
-            std::vector<int32_t> pair_first(std::max(n_pairs, 1), 0);
-            int64_t link_matches = 0;
-            {
-                std::vector<std::pair<int64_t, int32_t>> keyed(n_pairs);
-                for (int p = 0; p < n_pairs; ++p) {
-                    const int64_t a = std::min(pairs[2 * p], pairs[2 * p + 1]), c = std::max(pairs[2 * p], pairs[2 * p + 1]);
-                    keyed[p] = {a * n_shots + c, p};
-                }
-                std::sort(keyed.begin(), keyed.end());
-                for (int i = 0; i < n_pairs; ++i) {
-                    const int p = keyed[i].second;
-                    if (pairs[2 * p] == pairs[2 * p + 1]) continue;
-                    if (i == 0 || keyed[i - 1].first != keyed[i].first) {
-                        pair_first[p] = 1;
-                        link_matches += hoff[p + 1] - hoff[p];
-                    }
-                }
-            }
-            const uint32_t lcap = capacity_for(2 * link_matches), ccap = capacity_for(n_crec), ncap = capacity_for(n_nrec);
+            Slot* const S = call.S;
+            // 1. first pair per unordered shot pair: the only one whose matches link anything
+            std::vector<int32_t> pair_first;
+            const int64_t link_matches = plan::first_pairs(pairs, n_pairs, n_shots, hoff.data(), pair_first);
+            const uint32_t lcap = (uint32_t)plan::capacity_for(2 * link_matches), ccap = (uint32_t)plan::capacity_for(n_crec),
+                           ncap = (uint32_t)plan::capacity_for(n_nrec);
             const int n_total = n_cloud + n_new;
-
-            // device views of the inputs and outputs
-            std::vector<const float2*> kptr(std::max(n_shots, 1), nullptr);
-            const DMatchDev* dm = reinterpret_cast<const DMatchDev*>(matches);
-            const int64_t *doff = pair_offsets, *dco = cloud_origin_offsets, *dno = new_origin_offsets;
-            const int32_t *dcs = cloud_origin_shot, *dns = new_origin_shot;
-            const double *dcxy = cloud_origin_xy, *dnxy = new_origin_xy, *dcx = cloud_xyz, *dnx = new_xyz;
-            int32_t* do_shot = out_origin_shot;
-            double *do_xy = out_origin_xy, *do_xyz = out_xyz;
-            int64_t* do_off = out_origin_offsets;
-            // work buffers: requested below, all served by one allocation (Bufs::commit)
-            float2* kd = nullptr;
-            DMatchDev* md = nullptr;
-            int64_t *od = nullptr, *cod = nullptr, *nod = nullptr, *loff = nullptr, *ndest = nullptr;
-            int32_t *csd = nullptr, *nsd = nullptr, *nkd = nullptr, *prd = nullptr, *pfd = nullptr, *lslot = nullptr, *cslot = nullptr,
-                    *nslot = nullptr, *ent_shot = nullptr, *crec_point = nullptr, *nrec_elem = nullptr, *full = nullptr,
-                    *lcount = nullptr, *appd = nullptr;
-            double *cxyd = nullptr, *nxyd = nullptr, *cxd = nullptr, *nxd = nullptr;
-            const float2** kpd = nullptr;
-            unsigned long long* ent_pos = nullptr;
-            Summary* summ = nullptr;
-            if (inputs_on_device) {
-                for (int i = 0; i < n_shots; ++i) kptr[i] = reinterpret_cast<const float2*>(keypoints[i]);
-            } else {
-                int64_t nk = 0;
-                for (int i = 0; i < n_shots; ++i) {
-                    if (n_keypoints[i] < 0) MFAIL(SFMX_EINVAL, "negative keypoint count");
-                    nk += n_keypoints[i];
-                }
-                b.want(kd, nk);
-                b.want(md, n_matches);
-                b.want(od, n_pairs + 1);
-                b.want(cod, n_cloud + 1);
-                b.want(nod, n_new + 1);
-                b.want(csd, n_crec);
-                b.want(nsd, n_nrec);
-                b.want(cxyd, 2 * n_crec);
-                b.want(nxyd, 2 * n_nrec);
-                b.want(cxd, 3 * (int64_t)n_cloud);
-                b.want(nxd, 3 * (int64_t)n_new);
-                b.want(do_shot, n_crec + n_nrec);
-                b.want(do_xy, 2 * (n_crec + n_nrec));
-                b.want(do_xyz, 3 * (int64_t)n_total);
-                b.want(do_off, (int64_t)n_total + 1);
-            }
-            b.want(kpd, (int64_t)kptr.size());
-            b.want(nkd, n_shots);
-            b.want(prd, 2 * (int64_t)n_pairs);
-            b.want(pfd, n_pairs);
-            b.want(lslot, lcap);
-            b.want(cslot, ccap);
-            b.want(nslot, ncap);
-            b.want(ent_shot, 2 * n_matches);
-            b.want(ent_pos, 2 * n_matches);
-            b.want(crec_point, n_crec);
-            b.want(nrec_elem, n_nrec);
-            b.want(full, 1);
-            b.want(summ, n_new);
-            b.want(lcount, n_new);
-            b.want(loff, (int64_t)n_new + 1);
-            b.want(ndest, n_nrec);
-            b.want(appd, n_new);
-            if (!b.commit()) MFAIL(SFMX_ENOMEM, "device allocation failed");
-            if (!inputs_on_device) {
-                int64_t o = 0;
-                for (int i = 0; i < n_shots; ++i) {
-                    if (n_keypoints[i]) MCHK(hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st));
-                    kptr[i] = kd + o;
-                    o += n_keypoints[i];
-                }
-                if (n_matches) MCHK(hipMemcpyAsync(md, matches, sizeof(DMatchDev) * n_matches, hipMemcpyHostToDevice, st));
-                MCHK(hipMemcpyAsync(od, hoff.data(), sizeof(int64_t) * (n_pairs + 1), hipMemcpyHostToDevice, st));
-                MCHK(hipMemcpyAsync(cod, co, sizeof(int64_t) * (n_cloud + 1), hipMemcpyHostToDevice, st));
-                MCHK(hipMemcpyAsync(nod, no, sizeof(int64_t) * (n_new + 1), hipMemcpyHostToDevice, st));
-                if (n_crec) {
-                    MCHK(hipMemcpyAsync(csd, cs, sizeof(int32_t) * n_crec, hipMemcpyHostToDevice, st));
-                    MCHK(hipMemcpyAsync(cxyd, cxy, sizeof(double) * 2 * n_crec, hipMemcpyHostToDevice, st));
-                }
-                if (n_nrec) {
-                    MCHK(hipMemcpyAsync(nsd, ns, sizeof(int32_t) * n_nrec, hipMemcpyHostToDevice, st));
-                    MCHK(hipMemcpyAsync(nxyd, nxy, sizeof(double) * 2 * n_nrec, hipMemcpyHostToDevice, st));
-                }
-                if (n_cloud) MCHK(hipMemcpyAsync(cxd, cx, sizeof(double) * 3 * n_cloud, hipMemcpyHostToDevice, st));
-                MCHK(hipMemcpyAsync(nxd, nx, sizeof(double) * 3 * n_new, hipMemcpyHostToDevice, st));
-                dm = md; doff = od; dco = cod; dno = nod; dcs = csd; dns = nsd; dcxy = cxyd; dnxy = nxyd; dcx = cxd; dnx = nxd;
-            }
-            MCHK(hipMemcpyAsync(kpd, kptr.data(), sizeof(float2*) * kptr.size(), hipMemcpyHostToDevice, st));
-            if (n_shots) MCHK(hipMemcpyAsync(nkd, n_keypoints, sizeof(int32_t) * n_shots, hipMemcpyHostToDevice, st));
-            if (n_pairs) {
-                MCHK(hipMemcpyAsync(prd, pairs, sizeof(int32_t) * 2 * n_pairs, hipMemcpyHostToDevice, st));
-                MCHK(hipMemcpyAsync(pfd, pair_first.data(), sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, st));
-            }
-            Events events;
-            hipEvent_t* ev = events.e;
-            for (int i = 0; i < 6; ++i) MCHK(hipEventCreate(&ev[i]));
-            const Table tc{cslot, ccap, dcs, dcxy, crec_point}, tn{nslot, ncap, dns, dnxy, nrec_elem};
             const unsigned eb = (unsigned)((n_new + 255) / 256);
-            std::vector<Summary> hs(n_new);
-            std::vector<int32_t> hcount(n_new), hlist, htarget(n_new), happ;
-            std::vector<int64_t> hloff(n_new + 1, 0), hdest(n_nrec, -1), hout((size_t)n_total + 1, 0);
-            std::vector<double> hdist(n_new);
-            const SyncOnExit drain{st, &device_set};
-            int32_t hfull = 0;
+            // the host buffers of the call's copies are sized before anything is in flight
+            hs.resize(n_new); hcount.resize(n_new); htarget.resize(n_new); hdist.resize(n_new); happ.reserve(n_new);
+            hloff.assign((size_t)n_new + 1, 0); hdest.assign(n_nrec, -1); hout.assign((size_t)n_total + 1, 0);
             int n_app = 0;
+            float ms = 0.f, part = 0.f;
+            int64_t nk = 0;
+            for (int i = 0; H && i < n_shots; ++i) nk += n_keypoints[i];
 
-            // 2-4. tables, static probe, link count
-            MCHK(hipEventRecord(ev[0], st));
-            MCHK(hipMemsetAsync(lslot, 0xff, sizeof(int32_t) * lcap, st));
-            MCHK(hipMemsetAsync(cslot, 0xff, sizeof(int32_t) * ccap, st));
-            MCHK(hipMemsetAsync(nslot, 0xff, sizeof(int32_t) * ncap, st));
-            MCHK(hipMemsetAsync(full, 0, sizeof(int32_t), st));
+            // device block: [tables of the call | work buffers | (host inputs: graph, both clouds, the output cloud)]
+            BlockLayout L;
+            const float2** kpd;
+            int32_t *nkd, *prd, *pfd, *lslot, *cslot, *nslot, *ent_shot, *crec_point, *nrec_elem, *full, *lcount, *appd, *csd, *nsd, *osd;
+            int64_t *loff, *ndest, *od, *cod, *nod, *ood;
+            unsigned long long* ent_pos;
+            Summary* summ;
+            float2* kd;
+            sfmx_dmatch* md;
+            double *cxyd, *nxyd, *cxd, *nxd, *oxyd, *oxd;
+            L.want(kpd, n_shots);
+            L.want(nkd, n_shots);
+            L.want(prd, 2 * (size_t)n_pairs);
+            L.want(pfd, n_pairs);
+            const size_t b_tab = L.need;   // up to here: staged in pinned memory, one upload
+            L.want(lslot, lcap);
+            L.want(cslot, ccap);
+            L.want(nslot, ncap);
+            L.want(ent_shot, 2 * (size_t)n_matches);
+            L.want(ent_pos, 2 * (size_t)n_matches);
+            L.want(crec_point, n_crec);
+            L.want(nrec_elem, n_nrec);
+            L.want(full, 1);
+            L.want(summ, n_new);
+            L.want(lcount, n_new);
+            L.want(loff, (size_t)n_new + 1);
+            L.want(ndest, n_nrec);
+            L.want(appd, n_new);
+            L.want(kd, nk, H);
+            L.want(md, n_matches, H);
+            L.want(od, (size_t)n_pairs + 1, H);
+            L.want(cod, (size_t)n_cloud + 1, H);
+            L.want(nod, (size_t)n_new + 1, H);
+            L.want(csd, n_crec, H);
+            L.want(nsd, n_nrec, H);
+            L.want(cxyd, 2 * (size_t)n_crec, H);
+            L.want(nxyd, 2 * (size_t)n_nrec, H);
+            L.want(cxd, 3 * (size_t)n_cloud, H);
+            L.want(nxd, 3 * (size_t)n_new, H);
+            L.want(osd, (size_t)(n_crec + n_nrec), H);
+            L.want(oxyd, 2 * (size_t)(n_crec + n_nrec), H);
+            L.want(oxd, 3 * (size_t)n_total, H);
+            L.want(ood, (size_t)n_total + 1, H);
+            rc = call.reserve(L, b_tab);
+            if (rc != SFMX_OK) goto done;
+            if (n_shots) std::memcpy(call.pinned(nkd), n_keypoints, sizeof(int32_t) * n_shots);
+            if (n_pairs) {
+                std::memcpy(call.pinned(prd), pairs, sizeof(int32_t) * 2 * n_pairs);
+                std::memcpy(call.pinned(pfd), pair_first.data(), sizeof(int32_t) * n_pairs);
+            }
+            const float2** hk = call.pinned(kpd);
+            int64_t o = 0;
+            for (int i = 0; i < n_shots; ++i) {
+                if (H) {
+                    if (n_keypoints[i]) SFMX_HIP_CHK(hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st));
+                    hk[i] = kd + o;
+                    o += n_keypoints[i];
+                } else {
+                    hk[i] = reinterpret_cast<const float2*>(keypoints[i]);
+                }
+            }
+            SFMX_HIP_CHK(call.upload(b_tab));
+            // what the kernels read and write: the caller's device arrays or the staging copies
+            const DMatchDev* dm = reinterpret_cast<const DMatchDev*>(n_matches ? call.in(matches, md, n_matches) : matches);
+            const int64_t* doff = n_pairs ? call.in(pair_offsets, od, (size_t)n_pairs + 1) : pair_offsets;
+            const int64_t* dco = call.in(cloud_origin_offsets, cod, (size_t)n_cloud + 1);
+            const int64_t* dno = call.in(new_origin_offsets, nod, (size_t)n_new + 1);
+            const int32_t* dcs = n_crec ? call.in(cloud_origin_shot, csd, n_crec) : cloud_origin_shot;
+            const int32_t* dns = n_nrec ? call.in(new_origin_shot, nsd, n_nrec) : new_origin_shot;
+            const double* dcxy = n_crec ? call.in(cloud_origin_xy, cxyd, 2 * (size_t)n_crec) : cloud_origin_xy;
+            const double* dnxy = n_nrec ? call.in(new_origin_xy, nxyd, 2 * (size_t)n_nrec) : new_origin_xy;
+            const double* dcx = n_cloud ? call.in(cloud_xyz, cxd, 3 * (size_t)n_cloud) : cloud_xyz;
+            const double* dnx = call.in(new_xyz, nxd, 3 * (size_t)n_new);
+            SFMX_HIP_CHK(call.err);
+            int32_t* do_shot = call.out(out_origin_shot, osd);
+            double *do_xy = call.out(out_origin_xy, oxyd), *do_xyz = call.out(out_xyz, oxd);
+            int64_t* do_off = call.out(out_origin_offsets, ood);
+            const Table tc{cslot, ccap, dcs, dcxy, crec_point}, tn{nslot, ncap, dns, dnxy, nrec_elem};
+
+            // 2-4. tables, static probe, link count (timed span 1; every span ends in a stream synchronisation,
+            //      after which its time is read and the slot's two events are free for the next)
+            SFMX_HIP_CHK(hipEventRecord(S->e0, st));
+            SFMX_HIP_CHK(hipMemsetAsync(lslot, 0xff, sizeof(int32_t) * lcap, st));
+            SFMX_HIP_CHK(hipMemsetAsync(cslot, 0xff, sizeof(int32_t) * ccap, st));
+            SFMX_HIP_CHK(hipMemsetAsync(nslot, 0xff, sizeof(int32_t) * ncap, st));
+            SFMX_HIP_CHK(hipMemsetAsync(full, 0, sizeof(int32_t), st));
             if (n_matches && link_matches)
                 build_links_kernel<<<(unsigned)((n_matches + 255) / 256), 256, 0, st>>>(n_matches, n_pairs, doff, pfd, prd, dm, kpd, nkd,
                                                                                        F, lslot, lcap, ent_shot, ent_pos, full);
@@ -601,33 +517,40 @@ int sfmx_merge_pointcloud_3d2d(const sfmx_point2f* const* keypoints, const int32
                                                                                      nrec_elem, full);
             probe_kernel<false><<<eb, 256, 0, st>>>(n_new, dno, dns, dnxy, dnx, dcx, D, lslot, lcap, ent_shot, ent_pos, tc, tn, summ,
                                                     lcount, nullptr, nullptr);
-            MCHK(hipGetLastError());
-            MCHK(hipEventRecord(ev[1], st));
-            MCHK(hipMemcpyAsync(hs.data(), summ, sizeof(Summary) * n_new, hipMemcpyDeviceToHost, st));
-            MCHK(hipMemcpyAsync(hcount.data(), lcount, sizeof(int32_t) * n_new, hipMemcpyDeviceToHost, st));
-            MCHK(hipMemcpyAsync(&hfull, full, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            MCHK(hipStreamSynchronize(st));
-            if (hfull) MFAIL(SFMX_EINTERNAL, "a merge hash table filled up");
+            SFMX_HIP_CHK(hipGetLastError());
+            SFMX_HIP_CHK(hipEventRecord(S->e1, st));
+            SFMX_HIP_CHK(hipMemcpyAsync(hs.data(), summ, sizeof(Summary) * n_new, hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipMemcpyAsync(hcount.data(), lcount, sizeof(int32_t) * n_new, hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipMemcpyAsync(&hfull, full, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
+            if (hipEventElapsedTime(&part, S->e0, S->e1) == hipSuccess) ms += part;
+            if (hfull) { set_last_error("a merge hash table filled up"); rc = SFMX_EINTERNAL; goto done; }
             for (int e = 0; e < n_new; ++e) hloff[e + 1] = hloff[e] + hcount[e];
-            if (hloff[n_new] >= INT32_MAX) MFAIL(SFMX_ECAPACITY, "more than 2^31 links between the new elements: merge them in several calls");
+            if (hloff[n_new] >= INT32_MAX) {
+                set_last_error("more than 2^31 links between the new elements: merge them in several calls");
+                rc = SFMX_ECAPACITY;
+                goto done;
+            }
             hlist.resize(hloff[n_new]);
-            MCHK(hipEventRecord(ev[2], st));
-            if (hloff[n_new]) {
-                auto* llist = static_cast<int32_t*>(b.alloc(sizeof(int32_t) * (size_t)hloff[n_new]));
-                if (!llist) MFAIL(SFMX_ENOMEM, "device allocation failed");
-                MCHK(hipMemcpyAsync(loff, hloff.data(), sizeof(int64_t) * (n_new + 1), hipMemcpyHostToDevice, st));
+            if (hloff[n_new]) {   // the link lists (timed span 2)
+                BlockLayout LL;
+                int32_t* llist;
+                LL.want(llist, (size_t)hloff[n_new]);
+                const int orc = link_call.open(g_link_slot, device);   // the stream is idle here
+                if (orc != SFMX_OK) return orc;
+                if ((rc = link_call.reserve(LL, 0)) != SFMX_OK) goto done;
+                SFMX_HIP_CHK(hipEventRecord(S->e0, st));
+                SFMX_HIP_CHK(hipMemcpyAsync(loff, hloff.data(), sizeof(int64_t) * (n_new + 1), hipMemcpyHostToDevice, st));
                 probe_kernel<true><<<eb, 256, 0, st>>>(n_new, dno, dns, dnxy, dnx, dcx, D, lslot, lcap, ent_shot, ent_pos, tc, tn,
                                                        nullptr, nullptr, loff, llist);
-                MCHK(hipGetLastError());
-                MCHK(hipEventRecord(ev[3], st));
-                MCHK(hipMemcpyAsync(hlist.data(), llist, sizeof(int32_t) * hloff[n_new], hipMemcpyDeviceToHost, st));
-                MCHK(hipStreamSynchronize(st));
-            } else {
-                MCHK(hipEventRecord(ev[3], st));
+                SFMX_HIP_CHK(hipGetLastError());
+                SFMX_HIP_CHK(hipEventRecord(S->e1, st));
+                SFMX_HIP_CHK(hipMemcpyAsync(hlist.data(), llist, sizeof(int32_t) * hloff[n_new], hipMemcpyDeviceToHost, st));
+                SFMX_HIP_CHK(hipStreamSynchronize(st));
+                if (hipEventElapsedTime(&part, S->e0, S->e1) == hipSuccess) ms += part;
             }
 
             // 5a. targets, in element order (Scene.cpp:532-538 fold, :552-567 merge or append)
-            happ.reserve(n_new);
             int64_t n_static = 0, n_dynamic = 0;
             for (int e = 0; e < n_new; ++e) {
                 Summary s = hs[e];
@@ -699,47 +622,45 @@ int sfmx_merge_pointcloud_3d2d(const sfmx_point2f* const* keypoints, const int32
                 }
             }
 
-            // 6. scatter
-            if (n_nrec) MCHK(hipMemcpyAsync(ndest, hdest.data(), sizeof(int64_t) * n_nrec, hipMemcpyHostToDevice, st));
-            if (n_app) MCHK(hipMemcpyAsync(appd, happ.data(), sizeof(int32_t) * n_app, hipMemcpyHostToDevice, st));
-            MCHK(hipMemcpyAsync(do_off, hout.data(), sizeof(int64_t) * (n_out + 1), hipMemcpyHostToDevice, st));
-            MCHK(hipEventRecord(ev[4], st));
+            // 6. scatter (timed span 3)
+            if (n_nrec) SFMX_HIP_CHK(hipMemcpyAsync(ndest, hdest.data(), sizeof(int64_t) * n_nrec, hipMemcpyHostToDevice, st));
+            if (n_app) SFMX_HIP_CHK(hipMemcpyAsync(appd, happ.data(), sizeof(int32_t) * n_app, hipMemcpyHostToDevice, st));
+            SFMX_HIP_CHK(hipMemcpyAsync(do_off, hout.data(), sizeof(int64_t) * (n_out + 1), hipMemcpyHostToDevice, st));
+            SFMX_HIP_CHK(hipEventRecord(S->e0, st));
             {
                 const int64_t items = n_crec + n_nrec + n_out;
                 scatter_kernel<<<(unsigned)((items + 255) / 256), 256, 0, st>>>(n_crec, n_nrec, n_cloud, n_out, dco, crec_point, dcs, dcxy,
                                                                                dcx, dns, dnxy, dnx, ndest, appd, do_off, do_shot, do_xy,
                                                                                do_xyz);
             }
-            MCHK(hipGetLastError());
-            MCHK(hipEventRecord(ev[5], st));
-            if (inputs_on_device) {
-                MCHK(hipMemcpyAsync(out_target, htarget.data(), sizeof(int32_t) * n_new, hipMemcpyHostToDevice, st));
-                MCHK(hipMemcpyAsync(out_merge_distance, hdist.data(), sizeof(double) * n_new, hipMemcpyHostToDevice, st));
+            SFMX_HIP_CHK(hipGetLastError());
+            SFMX_HIP_CHK(hipEventRecord(S->e1, st));
+            if (!H) {
+                SFMX_HIP_CHK(hipMemcpyAsync(out_target, htarget.data(), sizeof(int32_t) * n_new, hipMemcpyHostToDevice, st));
+                SFMX_HIP_CHK(hipMemcpyAsync(out_merge_distance, hdist.data(), sizeof(double) * n_new, hipMemcpyHostToDevice, st));
             } else {
                 std::memcpy(out_target, htarget.data(), sizeof(int32_t) * n_new);
                 std::memcpy(out_merge_distance, hdist.data(), sizeof(double) * n_new);
                 std::memcpy(out_origin_offsets, hout.data(), sizeof(int64_t) * (n_out + 1));
-                MCHK(hipMemcpyAsync(out_xyz, do_xyz, sizeof(double) * 3 * n_out, hipMemcpyDeviceToHost, st));
+                SFMX_HIP_CHK(call.back(out_xyz, oxd, 3 * (size_t)n_out));
                 if (hout[n_out]) {
-                    MCHK(hipMemcpyAsync(out_origin_shot, do_shot, sizeof(int32_t) * hout[n_out], hipMemcpyDeviceToHost, st));
-                    MCHK(hipMemcpyAsync(out_origin_xy, do_xy, sizeof(double) * 2 * hout[n_out], hipMemcpyDeviceToHost, st));
+                    SFMX_HIP_CHK(call.back(out_origin_shot, osd, hout[n_out]));
+                    SFMX_HIP_CHK(call.back(out_origin_xy, oxyd, 2 * (size_t)hout[n_out]));
                 }
             }
-            MCHK(hipStreamSynchronize(st));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
+            if (hipEventElapsedTime(&part, S->e0, S->e1) == hipSuccess) ms += part;
             *out_n_points = n_out;
             *out_n_origins = hout[n_out];
-            float ms = 0.f, part = 0.f;
-            for (int i = 0; i < 6; i += 2) {
-                if (hipEventElapsedTime(&part, ev[i], ev[i + 1]) == hipSuccess) ms += part;
-            }
             g_last_ms = ms;
         }
     done:;
-    } catch (const std::bad_alloc&) {   // the host buffers; no exception crosses the ABI
+        rc = call.finish(rc, "sfmx_merge_pointcloud_3d2d");   // drains the stream after an error: the host buffers are alive
+    } catch (const std::bad_alloc&) {   // the host buffers: none is allocated with a copy to or from one in flight; no exception crosses the ABI
+        if (call.S) (void)hipStreamSynchronize(st);   // the copies up from the caller's arrays
         rc = SFMX_ENOMEM;
         set_last_error("host allocation failed");
     }
-    if (device_set && prev >= 0) (void)hipSetDevice(prev);
     return rc;
 }
 

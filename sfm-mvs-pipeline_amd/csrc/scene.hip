@@ -31,6 +31,7 @@
 #include "../../include/sfmx_scene.h"
 #include "device_call.hpp"
 #include "match_common.hpp"
+#include "scene_plan.hpp"
 
 namespace sfmx {
 namespace scene {
@@ -203,26 +204,112 @@ void count_kernel(int64_t n_origins, const int32_t* __restrict__ origin_shot, co
 
 thread_local float g_last_ms = -1.f;
 thread_local float g_count_ms = -1.f;
-Slot g_count_slot[64];   // csrc/device_call.hpp
+Slot g_slot[64];   // csrc/device_call.hpp; both entry points share it
 
-struct Bufs {
-    std::vector<void*> ptrs;
-    ~Bufs() { for (void* q : ptrs) (void)hipFree(q); }
-    void* alloc(size_t bytes) {
-        void* q = nullptr;
-        if (hipMalloc(&q, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-        ptrs.push_back(q);
-        return q;
+// ---- what both entry points do around their launches (the call frame: csrc/device_call.hpp) -----------------------
+
+// the checks of the graph's host arrays that need no device
+static int check_graph(const int32_t* n_keypoints, int32_t n_shots, const int32_t* pairs, int32_t n_pairs) {
+    if (!plan::counts_non_negative(n_keypoints, n_shots)) { set_last_error("negative keypoint count"); return SFMX_EINVAL; }
+    if (!plan::shots_in_range(pairs, n_pairs, n_shots)) { set_last_error("pair shot index out of range"); return SFMX_EINVAL; }
+    return SFMX_OK;
+}
+
+// After F.open: the pair offsets and the origin record count on the host, their checks, the tables of the call
+// (cand_of_shot[s]: the index of shot s among the candidates, -1 for the others).  SFMX_OK, or the status with the
+// error text set (the frame's tail names a HIP error).
+static int plan_call(const DeviceCall& F, const int32_t* n_keypoints, const int32_t* pairs, int32_t n_pairs,
+                     const int32_t* pair_active, const sfmx_dmatch* matches, const int64_t* pair_offsets,
+                     const int64_t* origin_offsets, int32_t n_points, const std::vector<int32_t>& cand_of_shot,
+                     std::vector<int64_t>& hoff, int64_t& n_origins, plan::Tables& T) {
+    hoff.assign((size_t)n_pairs + 1, 0);
+    if (F.host) {
+        if (n_pairs) std::memcpy(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1));
+        n_origins = origin_offsets[n_points];
+    } else if ((n_pairs && hipMemcpyAsync(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, F.st) != hipSuccess) ||
+               hipMemcpyAsync(&n_origins, origin_offsets + n_points, sizeof(int64_t), hipMemcpyDeviceToHost, F.st) != hipSuccess ||
+               hipStreamSynchronize(F.st) != hipSuccess) {
+        return SFMX_EDEVICE;
+    }
+    if (!plan::offsets_ascend(hoff.data(), n_pairs)) { set_last_error("pair offsets do not ascend from 0"); return SFMX_EINVAL; }
+    if (n_origins < 0 || (n_origins + 255) / 256 > INT32_MAX) { set_last_error("origin record count out of range"); return SFMX_EINVAL; }
+    if (hoff[n_pairs] && !matches) { set_last_error("null argument"); return SFMX_EINVAL; }
+    const int rc = plan::plan_tables(pairs, n_pairs, pair_active, hoff.data(), cand_of_shot.data(), F.host ? matches : nullptr,
+                                     n_keypoints, T);
+    if (rc != SFMX_OK) set_last_error(T.why);
+    return rc;
+}
+
+// The parts of the device block that both entry points have: the graph's small tables, which lie among the block's
+// pinned leading tables, and with host inputs the staging copies of the graph and of the origin records.
+struct Graph {
+    int32_t *nkd, *prd, *sd;
+    const float2** kpd;
+    float2* kd;
+    sfmx_dmatch* md;
+    int64_t* od;
+    double* xd;
+    // what the kernels read: the caller's device arrays or the staging copies, set by stage()
+    const DMatchDev* dm;
+    const int64_t* doff;
+    const int32_t* dshot;
+    const double* dxy;
+
+    void want_tables(BlockLayout& L, int32_t n_shots, int32_t n_pairs) {
+        L.want(nkd, n_shots);
+        L.want(prd, 2 * (size_t)n_pairs);
+        L.want(kpd, n_shots);
+    }
+    void want_staging(BlockLayout& L, bool H, const int32_t* n_keypoints, int32_t n_shots, int32_t n_pairs, int64_t n_matches,
+                      int64_t n_origins) {
+        int64_t nk = 0;
+        for (int i = 0; H && i < n_shots; ++i) nk += n_keypoints[i];
+        L.want(kd, nk, H);
+        L.want(md, n_matches, H);
+        L.want(od, (size_t)n_pairs + 1, H);
+        L.want(sd, n_origins, H);
+        L.want(xd, 2 * (size_t)n_origins, H);
+    }
+    // after F.reserve: fills the pinned twins of the tables and sends the host inputs on their way up
+    hipError_t stage(DeviceCall& F, const sfmx_point2f* const* keypoints, const int32_t* n_keypoints, int32_t n_shots,
+                     const int32_t* pairs, int32_t n_pairs, const sfmx_dmatch* matches, int64_t n_matches,
+                     const int64_t* pair_offsets, const int32_t* origin_shot, const double* origin_xy, int64_t n_origins) {
+        std::memcpy(F.pinned(nkd), n_keypoints, sizeof(int32_t) * n_shots);
+        if (n_pairs) std::memcpy(F.pinned(prd), pairs, sizeof(int32_t) * 2 * n_pairs);
+        const float2** hk = F.pinned(kpd);
+        int64_t o = 0;
+        for (int i = 0; i < n_shots; ++i) {
+            if (F.host) {
+                if (n_keypoints[i] && F.err == hipSuccess)
+                    F.err = hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, F.st);
+                hk[i] = kd + o;
+                o += n_keypoints[i];
+            } else {
+                hk[i] = reinterpret_cast<const float2*>(keypoints[i]);
+            }
+        }
+        dm = reinterpret_cast<const DMatchDev*>(n_matches ? F.in(matches, md, n_matches) : matches);
+        doff = n_pairs ? F.in(pair_offsets, od, (size_t)n_pairs + 1) : pair_offsets;
+        dshot = n_origins ? F.in(origin_shot, sd, n_origins) : origin_shot;
+        dxy = n_origins ? F.in(origin_xy, xd, 2 * (size_t)n_origins) : origin_xy;
+        return F.err;
     }
 };
+
+// the pinned twins of the table list (used) and of the exclusive scan of its match counts (first)
+static void fill_used(const plan::Tables& T, UsedPair* used, int32_t* first) {
+    for (size_t u = 0; u < T.tables.size(); ++u) {
+        const plan::Table& t = T.tables[u];
+        used[u] = UsedPair{t.pair, t.other_is_left, t.slot0, (int32_t)t.cap, t.cand};
+        first[u] = (int32_t)t.item0;
+    }
+}
 
 }  // namespace scene
 }  // namespace sfmx
 
 using namespace sfmx;
 using namespace sfmx::scene;
-
-#define SCHK(expr) do { if ((expr) != hipSuccess) { rc = SFMX_EDEVICE; set_last_error("HIP error in " #expr); goto done; } } while (0)
 
 extern "C" {
 
@@ -241,160 +328,88 @@ int sfmx_find_3d2d_matches(const sfmx_point2f* const* keypoints, const int32_t* 
         return SFMX_EINVAL;
     }
     if (shot < 0 || shot >= n_shots) { set_last_error("shot index out of range"); return SFMX_EINVAL; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_last_error("no HIP device visible"); return SFMX_EDEVICE; }
-    if (device < 0 || device >= ndev) { set_last_error("device index out of range"); return SFMX_EINVAL; }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_last_error("sfmx kernels are built for gfx950 only");
-        return SFMX_EDEVICE;
+    {
+        const int grc = check_graph(n_keypoints, n_shots, pairs, n_pairs);
+        if (grc != SFMX_OK) return grc;
     }
-    for (int p = 0; p < n_pairs; ++p)
-        if (pairs[2 * p] < 0 || pairs[2 * p] >= n_shots || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= n_shots) {
-            set_last_error("pair shot index out of range");
-            return SFMX_EINVAL;
-        }
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(device);
-    const hipStream_t st = (hipStream_t)stream;
+    if (!inputs_on_device && origin_offsets[n_points] && (!origin_shot || !origin_xy)) { set_last_error("null origin arrays"); return SFMX_EINVAL; }
+    DeviceCall F(stream, !inputs_on_device);
+    const hipStream_t st = F.st;
+    {
+        const int orc = F.open(g_slot, device);
+        if (orc != SFMX_OK) return orc;
+    }
+    Slot* const S = F.S;
     int rc = SFMX_OK;
     {
-        Bufs b;
-        std::vector<int64_t> hoff(n_pairs + 1, 0), hoo;
+        std::vector<int64_t> hoff;
+        std::vector<int32_t> cand_of_shot(n_shots, -1);
+        plan::Tables T;
         int64_t n_origins = 0;
-        // 1. first pair per other shot (Scene.cpp:389-394: find_if over the pair list)
-        std::vector<int32_t> first(n_shots, -1);
-        std::vector<UsedPair> used;
-        std::vector<int32_t> used_of_shot(n_shots, -1), used_first;
-        int64_t items = 0, slots = 0;
-        if (inputs_on_device) {
-            if (n_pairs) SCHK(hipMemcpyAsync(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
-            SCHK(hipMemcpyAsync(&n_origins, origin_offsets + n_points, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            SCHK(hipStreamSynchronize(st));
-        } else {
-            if (n_pairs) std::memcpy(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1));
-            n_origins = origin_offsets[n_points];
-            if (n_origins && (!origin_shot || !origin_xy)) { set_last_error("null origin arrays"); rc = SFMX_EINVAL; goto done; }
-        }
-        for (int p = 0; p < n_pairs; ++p) {
-            const int L = pairs[2 * p], R = pairs[2 * p + 1];
-            if (L == R) continue;
-            const int o = L == shot ? R : (R == shot ? L : -1);
-            if (o >= 0 && first[o] < 0) first[o] = p;
-        }
-        for (int o = 0; o < n_shots; ++o) {
-            const int p = first[o];
-            if (p < 0) continue;
-            const int64_t m = hoff[p + 1] - hoff[p];
-            if (m <= 0) continue;
-            int cap = 16;
-            while (cap < 2 * m) cap <<= 1;
-            used_of_shot[o] = (int32_t)used.size();
-            used.push_back(UsedPair{p, pairs[2 * p] == o ? 1 : 0, slots, cap, 0});
-            used_first.push_back((int32_t)items);
-            items += m;
-            slots += cap;
-        }
-        if (items >= INT32_MAX) { set_last_error("too many matches"); rc = SFMX_EINVAL; goto done; }
-        if (!inputs_on_device) {   // host validation of keypoint indices of the used pairs
-            for (const UsedPair& u : used)
-                for (int64_t i = hoff[u.pair]; i < hoff[u.pair + 1]; ++i) {
-                    const int L = pairs[2 * u.pair], R = pairs[2 * u.pair + 1];
-                    if (matches[i].queryIdx < 0 || matches[i].queryIdx >= n_keypoints[L] || matches[i].trainIdx < 0 ||
-                        matches[i].trainIdx >= n_keypoints[R]) {
-                        set_last_error("match index outside its image's keypoints");
-                        rc = SFMX_EINVAL;
-                        goto done;
-                    }
-                }
-        }
+        cand_of_shot[shot] = 0;   // the count's plan for one candidate and no mask (Scene.cpp:389-394)
+        rc = plan_call(F, n_keypoints, pairs, n_pairs, nullptr, matches, pair_offsets, origin_offsets, n_points, cand_of_shot, hoff,
+                       n_origins, T);
+        if (rc == SFMX_ECAPACITY) rc = SFMX_EINVAL;   // this entry point's code for too many matches
+        if (rc != SFMX_OK) goto done;
         {
-            // device copies of the inputs
-            std::vector<const float2*> kptr(std::max(n_shots, 1));
-            const DMatchDev* dm = reinterpret_cast<const DMatchDev*>(matches);
-            const int64_t* doff = pair_offsets;
-            const int32_t* dshot = origin_shot;
-            const double* dxy = origin_xy;
-            int32_t *dokp = out_keypoint, *dopair = out_pair;
-            float* doxy = out_xy;
-            if (inputs_on_device) {
-                for (int i = 0; i < n_shots; ++i) kptr[i] = reinterpret_cast<const float2*>(keypoints[i]);
-            } else {
-                int64_t nk = 0;
-                for (int i = 0; i < n_shots; ++i) nk += n_keypoints[i];
-                auto* kd = static_cast<float2*>(b.alloc(sizeof(float2) * nk));
-                auto* md = static_cast<DMatchDev*>(b.alloc(sizeof(DMatchDev) * std::max<int64_t>(hoff[n_pairs], 1)));
-                auto* od = static_cast<int64_t*>(b.alloc(sizeof(int64_t) * (n_pairs + 1)));
-                auto* sd = static_cast<int32_t*>(b.alloc(sizeof(int32_t) * std::max<int64_t>(n_origins, 1)));
-                auto* xd = static_cast<double*>(b.alloc(sizeof(double) * 2 * std::max<int64_t>(n_origins, 1)));
-                dokp = static_cast<int32_t*>(b.alloc(sizeof(int32_t) * std::max<int64_t>(n_origins, 1)));
-                dopair = static_cast<int32_t*>(b.alloc(sizeof(int32_t) * std::max<int64_t>(n_origins, 1)));
-                doxy = out_xy ? static_cast<float*>(b.alloc(sizeof(float) * 2 * std::max<int64_t>(n_origins, 1))) : nullptr;
-                if (!kd || !md || !od || !sd || !xd || !dokp || !dopair || (out_xy && !doxy)) { rc = SFMX_ENOMEM; goto done; }
-                int64_t o = 0;
-                for (int i = 0; i < n_shots; ++i) {
-                    if (n_keypoints[i]) SCHK(hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st));
-                    kptr[i] = kd + o;
-                    o += n_keypoints[i];
-                }
-                if (hoff[n_pairs]) SCHK(hipMemcpyAsync(md, matches, sizeof(DMatchDev) * hoff[n_pairs], hipMemcpyHostToDevice, st));
-                SCHK(hipMemcpyAsync(od, pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyHostToDevice, st));
-                if (n_origins) {
-                    SCHK(hipMemcpyAsync(sd, origin_shot, sizeof(int32_t) * n_origins, hipMemcpyHostToDevice, st));
-                    SCHK(hipMemcpyAsync(xd, origin_xy, sizeof(double) * 2 * n_origins, hipMemcpyHostToDevice, st));
-                }
-                dm = md; doff = od; dshot = sd; dxy = xd;
+            // device block: [tables of the call | hash tables | (host inputs: graph, origins, outputs)]
+            const bool H = F.host;
+            const size_t n_used = T.tables.size();
+            const int64_t n_matches = hoff[n_pairs];
+            BlockLayout L;
+            Graph G;
+            UsedPair* usd;
+            int32_t *ufd, *uos, *tv, *kpo, *pro;
+            unsigned long long* tk;
+            float* xyo;
+            L.want(usd, n_used);
+            L.want(ufd, n_used);
+            L.want(uos, n_shots);
+            G.want_tables(L, n_shots, n_pairs);
+            const size_t b_tab = L.need;   // up to here: staged in pinned memory, one upload
+            L.want(tk, T.slots);
+            L.want(tv, T.slots);
+            G.want_staging(L, H, n_keypoints, n_shots, n_pairs, n_matches, n_origins);
+            L.want(kpo, n_origins, H);
+            L.want(pro, n_origins, H);
+            L.want(xyo, 2 * (size_t)n_origins, H && out_xy);
+            rc = F.reserve(L, b_tab);
+            if (rc != SFMX_OK) goto done;
+            fill_used(T, F.pinned(usd), F.pinned(ufd));
+            int32_t* const used_of_shot = F.pinned(uos);
+            for (int s = 0; s < n_shots; ++s) used_of_shot[s] = -1;
+            for (size_t u = 0; u < n_used; ++u) used_of_shot[T.tables[u].other] = (int32_t)u;
+            SFMX_HIP_CHK(G.stage(F, keypoints, n_keypoints, n_shots, pairs, n_pairs, matches, n_matches, pair_offsets, origin_shot,
+                                 origin_xy, n_origins));
+            SFMX_HIP_CHK(F.upload(b_tab));
+            int32_t *dokp = F.out(out_keypoint, kpo), *dopair = F.out(out_pair, pro);
+            float* doxy = out_xy ? F.out(out_xy, xyo) : nullptr;
+            (void)hipEventRecord(S->e0, st);
+            if (T.slots) {
+                SFMX_HIP_CHK(hipMemsetAsync(tk, 0xff, sizeof(unsigned long long) * T.slots, st));
+                SFMX_HIP_CHK(hipMemsetAsync(tv, 0x7f, sizeof(int32_t) * T.slots, st));
             }
-            auto* kpd = static_cast<const float2**>(b.alloc(sizeof(float2*) * kptr.size()));
-            auto* nkd = static_cast<int32_t*>(b.alloc(sizeof(int32_t) * std::max(n_shots, 1)));
-            auto* prd = static_cast<int32_t*>(b.alloc(sizeof(int32_t) * 2 * std::max(n_pairs, 1)));
-            auto* usd = static_cast<UsedPair*>(b.alloc(sizeof(UsedPair) * std::max<size_t>(used.size(), 1)));
-            auto* ufd = static_cast<int32_t*>(b.alloc(sizeof(int32_t) * std::max<size_t>(used_first.size(), 1)));
-            auto* uos = static_cast<int32_t*>(b.alloc(sizeof(int32_t) * std::max(n_shots, 1)));
-            auto* tk = static_cast<unsigned long long*>(b.alloc(sizeof(unsigned long long) * std::max<int64_t>(slots, 1)));
-            auto* tv = static_cast<int32_t*>(b.alloc(sizeof(int32_t) * std::max<int64_t>(slots, 1)));
-            if (!kpd || !nkd || !prd || !usd || !ufd || !uos || !tk || !tv) { rc = SFMX_ENOMEM; goto done; }
-            SCHK(hipMemcpyAsync(kpd, kptr.data(), sizeof(float2*) * kptr.size(), hipMemcpyHostToDevice, st));
-            SCHK(hipMemcpyAsync(nkd, n_keypoints, sizeof(int32_t) * n_shots, hipMemcpyHostToDevice, st));
-            if (n_pairs) SCHK(hipMemcpyAsync(prd, pairs, sizeof(int32_t) * 2 * n_pairs, hipMemcpyHostToDevice, st));
-            if (!used.empty()) {
-                SCHK(hipMemcpyAsync(usd, used.data(), sizeof(UsedPair) * used.size(), hipMemcpyHostToDevice, st));
-                SCHK(hipMemcpyAsync(ufd, used_first.data(), sizeof(int32_t) * used_first.size(), hipMemcpyHostToDevice, st));
-            }
-            SCHK(hipMemcpyAsync(uos, used_of_shot.data(), sizeof(int32_t) * n_shots, hipMemcpyHostToDevice, st));
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            SCHK(hipEventCreate(&e0));
-            SCHK(hipEventCreate(&e1));
-            SCHK(hipEventRecord(e0, st));
-            if (slots) {
-                SCHK(hipMemsetAsync(tk, 0xff, sizeof(unsigned long long) * slots, st));
-                SCHK(hipMemsetAsync(tv, 0x7f, sizeof(int32_t) * slots, st));
-            }
-            if (items)
-                build_tables_kernel<<<(unsigned)((items + 255) / 256), 256, 0, st>>>(usd, ufd, (int)used.size(), items, doff, dm,
-                                                                                    kpd, nkd, prd, tk, tv);
+            if (T.items)
+                build_tables_kernel<<<(unsigned)((T.items + 255) / 256), 256, 0, st>>>(usd, ufd, (int)n_used, T.items, G.doff, G.dm,
+                                                                                      G.kpd, G.nkd, G.prd, tk, tv);
             if (n_origins)
-                lookup_kernel<<<(unsigned)((n_origins + 255) / 256), 256, 0, st>>>(n_origins, dshot, dxy, shot, n_shots, uos, usd,
-                                                                                 tk, tv, doff, dm, kpd, nkd, dokp, dopair, doxy);
-            SCHK(hipGetLastError());
-            SCHK(hipEventRecord(e1, st));
-            if (!inputs_on_device && n_origins) {
-                SCHK(hipMemcpyAsync(out_keypoint, dokp, sizeof(int32_t) * n_origins, hipMemcpyDeviceToHost, st));
-                SCHK(hipMemcpyAsync(out_pair, dopair, sizeof(int32_t) * n_origins, hipMemcpyDeviceToHost, st));
-                if (out_xy) SCHK(hipMemcpyAsync(out_xy, doxy, sizeof(float) * 2 * n_origins, hipMemcpyDeviceToHost, st));
+                lookup_kernel<<<(unsigned)((n_origins + 255) / 256), 256, 0, st>>>(n_origins, G.dshot, G.dxy, shot, n_shots, uos, usd,
+                                                                                 tk, tv, G.doff, G.dm, G.kpd, G.nkd, dokp, dopair, doxy);
+            (void)hipEventRecord(S->e1, st);
+            SFMX_HIP_CHK(hipGetLastError());
+            if (n_origins) {
+                SFMX_HIP_CHK(F.back(out_keypoint, kpo, n_origins));
+                SFMX_HIP_CHK(F.back(out_pair, pro, n_origins));
+                if (out_xy) SFMX_HIP_CHK(F.back(out_xy, xyo, 2 * (size_t)n_origins));
             }
-            SCHK(hipStreamSynchronize(st));
+            SFMX_HIP_CHK(hipStreamSynchronize(st));
             float ms = -1.f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
+            (void)hipEventElapsedTime(&ms, S->e0, S->e1);
             g_last_ms = ms;
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
         }
     done:;
+        rc = F.finish(rc, "sfmx_find_3d2d_matches");
     }
-    if (rc == SFMX_ENOMEM) set_last_error("device allocation failed");
-    if (prev >= 0) (void)hipSetDevice(prev);
     return rc;
 }
 
@@ -412,13 +427,10 @@ int sfmx_count_3d2d_matches(const sfmx_point2f* const* keypoints, const int32_t*
         set_last_error("null argument");
         return SFMX_EINVAL;
     }
-    for (int s = 0; s < n_shots; ++s)
-        if (n_keypoints[s] < 0) { set_last_error("negative keypoint count"); return SFMX_EINVAL; }
-    for (int p = 0; p < n_pairs; ++p)
-        if (pairs[2 * p] < 0 || pairs[2 * p] >= n_shots || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= n_shots) {
-            set_last_error("pair shot index out of range");
-            return SFMX_EINVAL;
-        }
+    {
+        const int grc = check_graph(n_keypoints, n_shots, pairs, n_pairs);
+        if (grc != SFMX_OK) return grc;
+    }
     std::vector<int32_t> cand_of_shot(n_shots, -1);
     for (int c = 0; c < n_candidates; ++c) {
         const int s = candidates[c];
@@ -427,162 +439,70 @@ int sfmx_count_3d2d_matches(const sfmx_point2f* const* keypoints, const int32_t*
         cand_of_shot[s] = c;
     }
     if (!inputs_on_device) {
-        if (origin_offsets[0] != 0) { set_last_error("origin offsets do not start at 0"); return SFMX_EINVAL; }
-        for (int p = 0; p < n_points; ++p)
-            if (origin_offsets[p + 1] < origin_offsets[p]) { set_last_error("origin offsets not ascending"); return SFMX_EINVAL; }
+        if (!plan::offsets_ascend(origin_offsets, n_points)) { set_last_error("origin offsets do not ascend from 0"); return SFMX_EINVAL; }
         if (origin_offsets[n_points] && (!origin_shot || !origin_xy)) { set_last_error("null origin arrays"); return SFMX_EINVAL; }
     }
     if (n_candidates == 0) { g_count_ms = 0.f; return SFMX_OK; }   // nothing to write
     DeviceCall F(stream, !inputs_on_device);
     const hipStream_t st = F.st;
     {
-        const int orc = F.open(g_count_slot, device);
+        const int orc = F.open(g_slot, device);
         if (orc != SFMX_OK) return orc;
     }
     Slot* const S = F.S;
     int rc = SFMX_OK;
     {
-        struct Entry { int32_t other, cand, pair; };
-        std::vector<int64_t> hoff(n_pairs + 1, 0);
-        std::vector<Entry> ent;
-        int64_t n_origins = 0, items = 0, slots = 0, nk = 0, n_matches = 0;
-        size_t n_used = 0;
-        if (inputs_on_device) {
-            if (n_pairs) SFMX_HIP_CHK(hipMemcpyAsync(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1), hipMemcpyDeviceToHost, st));
-            SFMX_HIP_CHK(hipMemcpyAsync(&n_origins, origin_offsets + n_points, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            SFMX_HIP_CHK(hipStreamSynchronize(st));
-        } else {
-            if (n_pairs) std::memcpy(hoff.data(), pair_offsets, sizeof(int64_t) * (n_pairs + 1));
-            n_origins = origin_offsets[n_points];
-        }
-        if (hoff[0] != 0) { set_last_error("pair offsets do not start at 0"); rc = SFMX_EINVAL; goto done; }
-        for (int p = 0; p < n_pairs; ++p)
-            if (hoff[p + 1] < hoff[p]) { set_last_error("pair offsets not ascending"); rc = SFMX_EINVAL; goto done; }
-        n_matches = hoff[n_pairs];
-        if (n_origins < 0 || (n_origins + 255) / 256 > INT32_MAX) { set_last_error("origin record count out of range"); rc = SFMX_EINVAL; goto done; }
-        if (n_matches && !matches) { set_last_error("null argument"); rc = SFMX_EINVAL; goto done; }
+        std::vector<int64_t> hoff;
+        plan::Tables T;
+        int64_t n_origins = 0;
         // per (origin shot o, candidate s): the first visible pair in list order joining {s, o} (Scene.cpp:389-394)
-        for (int p = 0; p < n_pairs; ++p) {
-            const int L = pairs[2 * p], R = pairs[2 * p + 1];
-            if (L == R || (pair_active && !pair_active[p])) continue;
-            if (cand_of_shot[L] >= 0) ent.push_back(Entry{R, cand_of_shot[L], p});
-            if (cand_of_shot[R] >= 0) ent.push_back(Entry{L, cand_of_shot[R], p});
-        }
-        std::stable_sort(ent.begin(), ent.end(), [](const Entry& a, const Entry& b) {
-            return a.other != b.other ? a.other < b.other : a.cand < b.cand;
-        });
-        for (size_t i = ent.size(); i-- > 1;)   // only the first of every (o, s) run counts
-            if (ent[i].other == ent[i - 1].other && ent[i].cand == ent[i - 1].cand) ent[i].pair = -1;
-        for (size_t i = 0; i < ent.size(); ++i) {   // a first pair without matches has no table: no match through it
-            const int p = ent[i].pair;
-            if (p < 0) continue;
-            const int64_t m = hoff[p + 1] - hoff[p];
-            if (m <= 0) { ent[i].pair = -1; continue; }
-            if (!inputs_on_device) {   // host validation of the keypoint indices of the pairs that are read
-                const int L = pairs[2 * p], R = pairs[2 * p + 1];
-                for (int64_t k = hoff[p]; k < hoff[p + 1]; ++k)
-                    if (matches[k].queryIdx < 0 || matches[k].queryIdx >= n_keypoints[L] || matches[k].trainIdx < 0 ||
-                        matches[k].trainIdx >= n_keypoints[R]) {
-                        set_last_error("match index outside its image's keypoints");
-                        rc = SFMX_EINVAL;
-                        goto done;
-                    }
-            }
-            if (m > ((int64_t)1 << 29)) { set_last_error("a match list beyond 2^29 entries"); rc = SFMX_ECAPACITY; goto done; }   // its table's capacity is an int32
-            ++n_used;
-            items += m;
-        }
-        if (items >= INT32_MAX || n_used >= (size_t)INT32_MAX) { set_last_error("too many matches"); rc = SFMX_ECAPACITY; goto done; }
-        if (!inputs_on_device)
-            for (int i = 0; i < n_shots; ++i) nk += n_keypoints[i];
+        rc = plan_call(F, n_keypoints, pairs, n_pairs, pair_active, matches, pair_offsets, origin_offsets, n_points, cand_of_shot, hoff,
+                       n_origins, T);
+        if (rc != SFMX_OK) goto done;
         {
-            // device block: [tables of the call | hash tables | (host inputs: keypoints, matches, offsets, origins, counts)]
+            // device block: [tables of the call | hash tables | (host inputs: graph, origins, counts)]
             const bool H = F.host;
+            const size_t n_used = T.tables.size();
+            const int64_t n_matches = hoff[n_pairs];
             BlockLayout L;
+            Graph G;
             UsedPair* usd;
-            int32_t *ufd, *tfd, *nkd, *ncd, *prd, *tv, *sd, *cd;
-            const float2** kpd;
+            int32_t *ufd, *tfd, *ncd, *tv, *cd;
             unsigned long long* tk;
-            float2* kd;
-            sfmx_dmatch* md;
-            int64_t* od;
-            double* xd;
             L.want(usd, n_used);
             L.want(ufd, n_used);
             L.want(tfd, (size_t)n_shots + 1);
-            L.want(nkd, n_shots);
             L.want(ncd, n_candidates);
-            L.want(prd, 2 * (size_t)n_pairs);
-            L.want(kpd, n_shots);
+            G.want_tables(L, n_shots, n_pairs);
             const size_t b_tab = L.need;   // up to here: staged in pinned memory, one upload
-            for (const Entry& en : ent) {
-                if (en.pair < 0) continue;
-                const int64_t m = hoff[en.pair + 1] - hoff[en.pair];
-                int64_t cap = 16;
-                while (cap < 2 * m) cap <<= 1;
-                slots += cap;
-            }
-            L.want(tk, slots);
-            L.want(tv, slots);
-            L.want(kd, nk, H);
-            L.want(md, n_matches, H);
-            L.want(od, (size_t)n_pairs + 1, H);
-            L.want(sd, n_origins, H);
-            L.want(xd, 2 * (size_t)n_origins, H);
+            L.want(tk, T.slots);
+            L.want(tv, T.slots);
+            G.want_staging(L, H, n_keypoints, n_shots, n_pairs, n_matches, n_origins);
             L.want(cd, n_candidates, H);
             rc = F.reserve(L, b_tab);
             if (rc != SFMX_OK) goto done;
-            UsedPair* hu = F.pinned(usd);
-            int32_t *huf = F.pinned(ufd), *htf = F.pinned(tfd);
-            size_t u = 0;
-            int64_t it = 0, sl = 0;
+            fill_used(T, F.pinned(usd), F.pinned(ufd));
+            int32_t* const htf = F.pinned(tfd);   // the tables of origin shot o: used[htf[o] .. htf[o + 1])
             for (int o = 0; o <= n_shots; ++o) htf[o] = 0;
-            for (const Entry& en : ent) {
-                if (en.pair < 0) continue;
-                const int64_t m = hoff[en.pair + 1] - hoff[en.pair];
-                int64_t cap = 16;
-                while (cap < 2 * m) cap <<= 1;
-                hu[u] = UsedPair{en.pair, pairs[2 * en.pair] == en.other ? 1 : 0, sl, (int32_t)cap, en.cand};
-                huf[u] = (int32_t)it;
-                ++htf[en.other + 1];
-                ++u;
-                it += m;
-                sl += cap;
-            }
+            for (const plan::Table& t : T.tables) ++htf[t.other + 1];
             for (int o = 0; o < n_shots; ++o) htf[o + 1] += htf[o];
-            std::memcpy(F.pinned(nkd), n_keypoints, sizeof(int32_t) * n_shots);
             for (int c = 0; c < n_candidates; ++c) F.pinned(ncd)[c] = n_keypoints[candidates[c]];
-            if (n_pairs) std::memcpy(F.pinned(prd), pairs, sizeof(int32_t) * 2 * n_pairs);
-            const float2** hk = F.pinned(kpd);
-            int64_t o = 0;
-            for (int i = 0; i < n_shots; ++i) {
-                if (H) {
-                    if (n_keypoints[i]) SFMX_HIP_CHK(hipMemcpyAsync(kd + o, keypoints[i], sizeof(float2) * n_keypoints[i], hipMemcpyHostToDevice, st));
-                    hk[i] = kd + o;
-                    o += n_keypoints[i];
-                } else {
-                    hk[i] = reinterpret_cast<const float2*>(keypoints[i]);
-                }
-            }
+            SFMX_HIP_CHK(G.stage(F, keypoints, n_keypoints, n_shots, pairs, n_pairs, matches, n_matches, pair_offsets, origin_shot,
+                                 origin_xy, n_origins));
             SFMX_HIP_CHK(F.upload(b_tab));
-            const DMatchDev* dm = reinterpret_cast<const DMatchDev*>(n_matches ? F.in(matches, md, n_matches) : matches);
-            const int64_t* doff = n_pairs ? F.in(pair_offsets, od, (size_t)n_pairs + 1) : pair_offsets;
-            const int32_t* dshot = n_origins ? F.in(origin_shot, sd, n_origins) : origin_shot;
-            const double* dxy = n_origins ? F.in(origin_xy, xd, 2 * (size_t)n_origins) : origin_xy;
-            SFMX_HIP_CHK(F.err);
             int32_t* dcount = F.out(out_count, cd);
             (void)hipEventRecord(S->e0, st);
             SFMX_HIP_CHK(hipMemsetAsync(dcount, 0, sizeof(int32_t) * n_candidates, st));
-            if (slots) {
-                SFMX_HIP_CHK(hipMemsetAsync(tk, 0xff, sizeof(unsigned long long) * slots, st));
-                SFMX_HIP_CHK(hipMemsetAsync(tv, 0x7f, sizeof(int32_t) * slots, st));
+            if (T.slots) {
+                SFMX_HIP_CHK(hipMemsetAsync(tk, 0xff, sizeof(unsigned long long) * T.slots, st));
+                SFMX_HIP_CHK(hipMemsetAsync(tv, 0x7f, sizeof(int32_t) * T.slots, st));
             }
-            if (items)
-                build_tables_kernel<<<(unsigned)((items + 255) / 256), 256, 0, st>>>(usd, ufd, (int)n_used, items, doff, dm, kpd,
-                                                                                    nkd, prd, tk, tv);
-            if (items && n_origins)
-                count_kernel<<<(unsigned)((n_origins + 255) / 256), 256, 0, st>>>(n_origins, dshot, dxy, n_shots, tfd, usd, tk, tv,
-                                                                                doff, dm, ncd, n_candidates, dcount);
+            if (T.items)
+                build_tables_kernel<<<(unsigned)((T.items + 255) / 256), 256, 0, st>>>(usd, ufd, (int)n_used, T.items, G.doff, G.dm,
+                                                                                      G.kpd, G.nkd, G.prd, tk, tv);
+            if (T.items && n_origins)
+                count_kernel<<<(unsigned)((n_origins + 255) / 256), 256, 0, st>>>(n_origins, G.dshot, G.dxy, n_shots, tfd, usd, tk, tv,
+                                                                                G.doff, G.dm, ncd, n_candidates, dcount);
             (void)hipEventRecord(S->e1, st);
             SFMX_HIP_CHK(hipGetLastError());
             SFMX_HIP_CHK(F.back(out_count, cd, n_candidates));

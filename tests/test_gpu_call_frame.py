@@ -1,27 +1,34 @@
-"""GPU: the life of a per-device slot across calls (csrc/device_call.hpp), for the six entry points that use it:
-homography ratios, triangulation, relative pose, registration pose, distinct 3D-2D points, cloud neighbour distances.
+"""GPU: the life of a per-device slot across calls (csrc/device_call.hpp), for nine entry points that use it:
+homography ratios, triangulation, relative pose, registration pose, distinct 3D-2D points, cloud neighbour distances,
+the 3D-2D search and its count (one slot for both), the cloud merge (a slot for the call and one for its link list).
 
 The parity tests of each module check one call against its restatement.  Here one process makes small and large
 calls in turn on the same slot, with host and with device arrays: the device block regrows for the large call
 (four copies of the small one's pairs or sets, more than 1.25 x its need, wherever no earlier test of the process
 has grown that slot further), is reused by the next small one, and its host-staging parts come and go.  Every pair
 and set seeds its own RNG, so the large call's outputs are the small call's repeated; the cloud, where copies would
-be duplicates, uses the golden cloud and one of four times as many points against tests/cloud_ref.py.  A call that
-the kernels refuse (a match index past its image's keypoints, device inputs) leaves the slot usable.
+be duplicates, uses the golden cloud and one of four times as many points against tests/cloud_ref.py; the 3D-2D
+search, its count and the merge use a small and a large case of their own suites against the oracle and
+tests/merge_ref.py.  A call that is refused after its slot was opened (a match index past its image's keypoints:
+found by the kernels with device inputs, on the host with host inputs for the 3D-2D search and its count; for the
+merge, offsets read back from the device that do not start at 0) leaves the slot usable.
 Everything is compared as bytes, so NaN outputs count."""
 import numpy as np
 import pytest
 import torch
 
-from sfmx import cloud, homography, pnp, pose, triangulate
+from sfmx import cloud, homography, pnp, pose, scene, triangulate
 from sfmx.matching import DMATCH_DTYPE
 import cloud_cases
 import cloud_ref
 import fixtures
 import homog_cases
+import merge_cases
+import merge_ref
 import pnp_cases
 import pnp_ref
 import pose_cases
+import scene_cases
 import tri_cases
 
 pytestmark = pytest.mark.gpu
@@ -213,8 +220,139 @@ class Cloud:
         return self.ref[reps]
 
 
+class Scene3d2d:
+    """The 3D-2D search for one shot and its count for every shot, which share one slot: the small case is
+    scene_cases.edge_case(), the large one scene_cases.scene_case(6, 1200, seed=5), both against the oracle's
+    find_3d2d_matches.  The search's block, from the part sizes of csrc/scene.hip (every part rounded up to 256
+    bytes): small 2 048 bytes with device inputs (six tables, two hash tables of 32 slots) and 4 352 with host inputs;
+    large 10 752 (three pairs with shot 2 hold matches, 768 slots of 12 bytes) and 133 888.  The count's tables serve
+    every shot and are larger still."""
+    SHOT = {1: 0, REPS: 2}
+
+    _SHARED = None   # the cases and the oracle's answers, computed once for both entry points
+
+    def __init__(self):
+        if Scene3d2d._SHARED is None:
+            Scene3d2d._SHARED = self.cases_and_answers()
+        self.case, self.found, self.counts = Scene3d2d._SHARED
+
+    def cases_and_answers(self):
+        from oracle import oracle
+        self.case = {1: scene_cases.edge_case(), REPS: scene_cases.scene_case(6, 1200, seed=5)}
+        self.found, self.counts = {}, {}
+        for r, c in self.case.items():
+            per_shot = [oracle.find_3d2d_matches(*c, s) for s in range(len(c[0]))]
+            k, p = per_shot[self.SHOT[r]]
+            xy = np.full((len(k), 2), np.nan, np.float32)
+            xy[k >= 0] = c[0][self.SHOT[r]][k[k >= 0]]
+            self.found[r] = dict(keypoint=k.astype(np.int32), pair=p.astype(np.int32), xy=xy)
+            self.counts[r] = {"count": np.array([(k >= 0).sum() for k, _ in per_shot], np.int32)}
+        assert (self.found[1]["keypoint"] >= 0).sum() == 4 and (self.found[REPS]["keypoint"] >= 0).sum() > 100
+        return self.case, self.found, self.counts
+
+    def restatement(self):
+        return self.expected(1)
+
+    def tiled(self, a, reps):
+        return self.expected(reps)
+
+    def device_arrays(self, reps, m):
+        kps, pairs, m0, off, oo, osh, oxy = self.case[reps]
+        d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        return [d(k) for k in kps], [d(a) for a in ((m0 if m is None else m).view(np.uint8), off, oo, osh, oxy)]
+
+    def bad_matches(self):
+        """Host inputs: the index is found on the host, after the slot was opened (device inputs are not read there)."""
+        bad = self.case[1][2].copy()
+        bad["trainIdx"][1] = len(self.case[1][0][1])   # pair 0 (0, 1): read for shot 0 and by the count
+        return bad
+
+    REFUSED_ON_DEVICE = False
+
+
+class Find3d2d(Scene3d2d):
+    def expected(self, reps):
+        return self.found[reps]
+
+    def run(self, reps, dev, m=None):
+        kps, pairs, m0, off, oo, osh, oxy = self.case[reps]
+        shot = self.SHOT[reps]
+        if not dev:
+            k, p, xy = scene.find_3d2d_matches(kps, pairs, m0 if m is None else m, off, oo, osh, oxy, shot)
+            return dict(keypoint=k, pair=p, xy=xy)
+        dk, (dm, doff, doo, dsh, dxy) = self.device_arrays(reps, m)
+        n = len(osh)
+        out = dict(keypoint=torch.full((n,), -7, dtype=torch.int32, device="cuda"),
+                   pair=torch.full((n,), -7, dtype=torch.int32, device="cuda"),
+                   xy=torch.zeros((n, 2), dtype=torch.float32, device="cuda"))
+        torch.cuda.synchronize()
+        scene.find_3d2d_matches_device([t.data_ptr() for t in dk], [len(k) for k in kps], pairs, dm.data_ptr(), doff.data_ptr(),
+                                       doo.data_ptr(), len(oo) - 1, dsh.data_ptr(), dxy.data_ptr(), shot,
+                                       out["keypoint"].data_ptr(), out["pair"].data_ptr(), out["xy"].data_ptr())
+        return to_numpy(out)
+
+
+class Count3d2d(Scene3d2d):
+    def expected(self, reps):
+        return self.counts[reps]
+
+    def run(self, reps, dev, m=None):
+        kps, pairs, m0, off, oo, osh, oxy = self.case[reps]
+        cand = list(range(len(kps)))
+        if not dev:
+            return {"count": scene.count_3d2d_matches(kps, pairs, m0 if m is None else m, off, oo, osh, oxy, cand)}
+        dk, (dm, doff, doo, dsh, dxy) = self.device_arrays(reps, m)
+        out = torch.full((len(cand),), -7, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        scene.count_3d2d_matches_device([t.data_ptr() for t in dk], [len(k) for k in kps], pairs, dm.data_ptr(), doff.data_ptr(),
+                                        doo.data_ptr(), len(oo) - 1, dsh.data_ptr(), dxy.data_ptr(), cand, out.data_ptr())
+        return to_numpy({"count": out})
+
+
+class Merge:
+    """The small case is the known answer `linked_near` (one new element: no links among new elements, so the call
+    makes no use of the link-list slot), the large one merge_cases.scene_case() against tests/merge_ref.py, whose
+    dynamic merges are merges through a link between two new elements: that call grows the link-list slot."""
+    KEYS = ("xyz", "origin_offsets", "origin_shot", "origin_xy", "target", "merge_distance")
+
+    def __init__(self):
+        small, known = merge_cases.known_cases()["linked_near"]
+        c = merge_cases.scene_case()
+        self.args = {1: small, REPS: (*merge_cases.args(c), merge_cases.D_MID, 20.0)}
+        stats = {1: {}, REPS: {}}
+        self.ref = {r: merge_ref.merge(*a, stats=stats[r]) for r, a in self.args.items()}
+        assert_same(self.ref[1], known, "merge: the known answer")
+        assert len(small[8]) == 1 and stats[1]["dynamic"] == 0 and stats[REPS]["dynamic"] > 0
+
+    def restatement(self):
+        return self.ref[1]
+
+    def tiled(self, a, reps):
+        return self.ref[reps]
+
+    def run(self, reps, dev, m=None, new_offsets=None):
+        kps, pairs, m, off, cx, co, cs, cxy, nx, no, ns, nxy, D, F = self.args[reps]
+        if not dev:
+            r = scene.merge_pointcloud_3d2d(kps, pairs, m, off, cx, co, cs, cxy, nx, no, ns, nxy, D, F)
+        else:
+            d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+            dk, dm, do = [d(k) for k in kps], d(m.view(np.uint8)), d(off)
+            clouds = [d(a) for a in (cx, co, cs, cxy, nx, no if new_offsets is None else new_offsets, ns, nxy)]
+            r = to_numpy(scene.merge_pointcloud_3d2d_device([t.data_ptr() for t in dk], [len(k) for k in kps], pairs, dm.data_ptr(),
+                                                            do.data_ptr(), *clouds, D, F))
+        links = scene.merge_last_stats()["links"]
+        assert (links > 0) == (reps == REPS), (reps, links)
+        return {k: r[k] for k in self.KEYS}
+
+    REFUSED = "new origin offsets"
+
+    def refused_call(self):
+        """Device inputs: the offsets are read back and refused after the slot was opened."""
+        self.run(1, True, new_offsets=np.array([1, 2], np.int64))
+
+
 ENTRIES = {"homography": Homography, "triangulate": Triangulate, "pose": Pose, "register": Register, "distinct": Distinct,
-           "cloud": Cloud}
+           "cloud": Cloud, "find_3d2d": Find3d2d, "count_3d2d": Count3d2d, "merge": Merge}
 _CACHE = {}
 
 
@@ -253,10 +391,27 @@ def test_host_and_device_calls_alternate_on_one_slot(name):
     assert_same(e.run(1, False), first, "host small again")
 
 
-@pytest.mark.parametrize("name", ["triangulate", "pose"])
+@pytest.mark.parametrize("name", ["triangulate", "pose", "find_3d2d", "count_3d2d", "merge"])
 def test_call_refused_by_the_kernels_leaves_the_slot_usable(name):
     e, first = entry(name)
-    with pytest.raises(ValueError, match="keypoints"):
-        e.run(1, True, e.bad_matches())
+    with pytest.raises(ValueError, match=getattr(e, "REFUSED", "keypoints")):
+        if hasattr(e, "refused_call"):
+            e.refused_call()
+        else:
+            e.run(1, getattr(e, "REFUSED_ON_DEVICE", True), e.bad_matches())
     assert_same(e.run(1, True), first, "device call after the refused one")
     assert_same(e.run(1, False), first, "host call after the refused one")
+
+
+@pytest.mark.parametrize("dev", [False, True], ids=["host", "device"])
+def test_find_and_count_take_turns_on_their_slot(dev):
+    """sfmx_find_3d2d_matches and sfmx_count_3d2d_matches lay their blocks out differently in the same slot."""
+    f, f_small = entry("find_3d2d")
+    c, c_small = entry("count_3d2d")
+    assert_same(f.run(1, dev), f_small, "find small")
+    assert_same(c.run(REPS, dev), c.expected(REPS), "count large")
+    assert_same(f.run(1, not dev), f_small, "find small after count large")
+    assert_same(f.run(REPS, dev), f.expected(REPS), "find large")
+    assert_same(c.run(1, dev), c_small, "count small after find large")
+    assert_same(c.run(REPS, not dev), c.expected(REPS), "count large again")
+    assert_same(f.run(1, dev), f_small, "find small again")

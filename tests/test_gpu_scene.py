@@ -32,6 +32,31 @@ def test_scene_exact_every_shot(seed):
         assert (gk >= 0).sum() > 0
 
 
+def test_invalid_arguments_are_the_counts():
+    """The checks of sfmx_count_3d2d_matches for the one candidate `shot`: only the lists that are read are checked."""
+    kps, pairs, m, off, oo, osh, oxy = scene_cases.edge_case()
+    good = scene.find_3d2d_matches(kps, pairs, m, off, oo, osh, oxy, 0)
+    for bad in ([0, 3, 2, 8, 9, 9], [1, 3, 6, 8, 9, 9]):
+        with pytest.raises(ValueError, match="pair offsets"):
+            scene.find_3d2d_matches(kps, pairs, m, np.array(bad, np.int64), oo, osh, oxy, 0)
+    bp = pairs.copy()
+    bp[3, 1] = 4
+    with pytest.raises(ValueError, match="pair shot"):
+        scene.find_3d2d_matches(kps, bp, m, off, oo, osh, oxy, 0)
+    with pytest.raises(ValueError, match="shot index"):
+        scene.find_3d2d_matches(kps, pairs, m, off, oo, osh, oxy, 4)
+    bm = m.copy()
+    bm["queryIdx"][4] = 12                      # pair 1 (2, 0): read for shot 0
+    with pytest.raises(ValueError, match="keypoints"):
+        scene.find_3d2d_matches(kps, pairs, bm, off, oo, osh, oxy, 0)
+    bm = m.copy()
+    bm["trainIdx"][8] = -1                      # pair 3 (1, 2): not read for shot 0
+    for g, e in zip(scene.find_3d2d_matches(kps, pairs, bm, off, oo, osh, oxy, 0), good):
+        assert np.array_equal(g, e, equal_nan=True)
+    for g, e in zip(scene.find_3d2d_matches(kps, pairs, m, off, oo, osh, oxy, 0), good):   # the slot is usable
+        assert np.array_equal(g, e, equal_nan=True)
+
+
 def test_device_inputs():
     kps, pairs, m, off, oo, osh, oxy = scene_cases.scene_case(6, 1200, seed=5)
     hk, hp, hxy = scene.find_3d2d_matches(kps, pairs, m, off, oo, osh, oxy, 2)
