@@ -196,6 +196,20 @@ typedef struct sfmx_ba_plan_info {
 } sfmx_ba_plan_info;
 int sfmx_ba_plan(int32_t n_cams, const uint8_t* adj, int32_t order, sfmx_ba_plan_info* info, int32_t* camrow,
                  int32_t* leaves, int32_t leaves_cap, int32_t* tasks, int32_t tasks_cap, int32_t* src, int32_t src_cap);
+/* The row-level zero structure the solver derives for the same plan (host only), i.e. what its one-launch
+ * factorization skips.  Optional outputs: src_mask[4 * info.src] rows (ra, rb, ka, kb) per src entry
+ * (task, source k): bit q of ra / rb = the 16-row strip q of A_ak / A_bk can be nonzero, bit q of ka / kb
+ * = their 4-column chunk q can; pad_panels[info.tiles]: bit q = rows 16q .. 16q + 15 of the tile are
+ * identity padding; item_mask[4 * n] rows (x, y, z, w), exactly the per-item words the solver uploads, in
+ * launch order (the leaves, then per level each task's sources), n = info.leaves + info.src:
+ * x = ra | rb << 4 | the column tiles of G = A_ak W_k << 8 | the inverted tile's padding panels << 12 |
+ * the panels swept before the update << 16, y = the chunks of W_k rows the item loads (ka with every
+ * chunk between its lowest and its highest set: the product runs over that whole range), z = kb, w = 0;
+ * item_src[n]: the item's src entry, -1 for a leaf.  A pair of cameras counts as co-visible when either
+ * adj[a][b] or adj[b][a] is set.  Capacities in rows.  Returns n, or SFMX_ECAPACITY / SFMX_EINVAL. */
+int sfmx_ba_plan_masks(int32_t n_cams, const uint8_t* adj, int32_t order, int32_t* src_mask, int32_t src_cap,
+                       int32_t* pad_panels, int32_t tiles_cap, int32_t* item_mask, int32_t* item_src,
+                       int32_t items_cap);
 
 /* Pose conversions of CeresUtils (util/CeresUtils.h:90-148): 3x4 [R|t]
  * row-major <-> Ceres pose {angle-axis, t}, via ceres::RotationMatrixToAngleAxis /

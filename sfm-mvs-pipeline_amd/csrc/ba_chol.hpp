@@ -277,6 +277,10 @@ constexpr int CHOL_TRACE_MAX = 512;
 #ifdef SFMX_DIAG
 __device__ long long g_chol_trace[CHOL_TRACE_MAX][16];
 #define CHOL_TRACE(tk, i) do { if (threadIdx.x == 0 && (tk) < CHOL_TRACE_MAX) g_chol_trace[tk][i] = wall_clock64(); } while (0)
+// SFMX_BA_POISON (diag.hpp; set with the plan, ba_solver.hip ensure_plan): chol_factor fills its W_k buffer
+// with quiet NaNs before it loads the W_k rows, so a product over a row the item did not load gives NaN
+// every time instead of whatever an earlier workgroup left in LDS
+__device__ int g_chol_poison;
 #else
 #define CHOL_TRACE(tk, i) do { } while (0)
 #endif
@@ -806,7 +810,8 @@ void chol_factor(double* __restrict__ S, int npad, double* __restrict__ R, const
     const int tk = sh[0];
     const int4 it = items[tk], nd = need[tk];
     // r06 row masks (ba_plan.cpp row_masks): x = ra | rb << 4 | G's column tiles << 8 | the inverted
-    // tile's padding panels << 12, y = ka, z = kb (wave-uniform)
+    // tile's padding panels << 12, y = ka with every chunk between its lowest and highest set (the W_k rows
+    // loaded = the range G's product runs over; ba_plan.cpp item_masks), z = kb (wave-uniform)
     const int4 mk0 = imask[tk];
     const int mx = __builtin_amdgcn_readfirstlane(mk0.x), mka = __builtin_amdgcn_readfirstlane(mk0.y),
               mkb = __builtin_amdgcn_readfirstlane(mk0.z);
@@ -885,6 +890,12 @@ void chol_factor(double* __restrict__ S, int npad, double* __restrict__ R, const
         if (tid == 0) wait_ver(tver_id(k, k), nd.z - 1);   // W_k stored (its R rows may still be in flight)
         __syncthreads();
         CHOL_TRACE(tk, 2);
+#ifdef SFMX_DIAG
+        if (g_chol_poison) {   // SFMX_BA_POISON: every row the load below leaves out reads as NaN
+            for (int e = tid; e < NB * LDT; e += NTH) (&sm.m[0][0])[e] = __builtin_nan("");
+            __syncthreads();
+        }
+#endif
         tile_load_wt_rows(sm.m, rW, (size_t)k * NB * NB, NB, mka);             // W_k (the rows G reads)
         __syncthreads();
         CHOL_TRACE(tk, 3);

@@ -284,11 +284,17 @@ void build(int C, const std::vector<std::vector<int>>& g, const std::vector<std:
 
 }  // namespace
 
-void make_plan(int C, const std::vector<char>& adj, int order_mode, FactorPlan& out) {
-    std::vector<std::vector<int>> g(C);   // co-visibility lists (either triangle of adj)
+void make_plan(int C, const std::vector<char>& adj_in, int order_mode, FactorPlan& out) {
+    // the symmetric closure, once: the graph and the row masks read the same pattern whichever
+    // triangle(s) of a pair the caller set
+    std::vector<char> adj((size_t)C * C, 0);
     for (int a = 0; a < C; ++a)
         for (int b = 0; b < C; ++b)
-            if (a != b && (adj[(size_t)a * C + b] || adj[(size_t)b * C + a])) g[a].push_back(b);
+            adj[(size_t)a * C + b] = a != b && (adj_in[(size_t)a * C + b] || adj_in[(size_t)b * C + a]);
+    std::vector<std::vector<int>> g(C);   // co-visibility lists
+    for (int a = 0; a < C; ++a)
+        for (int b = 0; b < C; ++b)
+            if (adj[(size_t)a * C + b]) g[a].push_back(b);
     std::vector<std::vector<int>> natural;
     if (C > 0) {
         natural.emplace_back(C);
@@ -402,6 +408,52 @@ void row_masks(const FactorPlan& P, const std::vector<char>& adj, std::vector<Ro
         }
 }
 
+void item_masks(const FactorPlan& P, std::vector<int>& tpre, std::vector<ItemMask>& imask, std::vector<int>* item_src) {
+    constexpr int NWP = NBP / 16;   // 16-row panels (= 16-column tiles) per tile
+    const std::vector<RowMask>& smask = P.src_mask;
+    const std::vector<int>& padp = P.pad_panels;
+    // r06: per task, the panels an inverting one-source task sweeps before its update (the ones
+    // outside A_ak's row strips and not padding); every factorization form uses the same order
+    tpre.assign(std::max<size_t>(P.tasks.size(), 1), 0);
+    for (int l = 0; l < P.height; ++l)
+        for (int t = P.task_start[l]; t < P.task_start[l + 1]; ++t) {
+            const PlanTask& tk = P.tasks[t];
+            const bool inv = (t - P.task_start[l]) < P.ninv[l];
+            if (inv && tk.a == tk.b && tk.s1 - tk.s0 == 1)
+                tpre[t] = ~smask[tk.s0].ra & ((1 << NWP) - 1) & ~padp[tk.a];
+        }
+    imask.clear();
+    if (item_src) item_src->clear();
+    for (int k : P.leaves) {
+        imask.push_back(ItemMask{padp[k] << 12, 0, 0, 0});
+        if (item_src) item_src->push_back(-1);
+    }
+    for (int l = 0; l < P.height; ++l)
+        for (int t = P.task_start[l]; t < P.task_start[l + 1]; ++t) {
+            const PlanTask& tk = P.tasks[t];
+            const bool inv = (t - P.task_start[l]) < P.ninv[l];
+            for (int s = tk.s0; s < tk.s1; ++s) {
+                const RowMask& rm = smask[s];
+                // G's column tiles: all for a diagonal task (G^T is stored for the back solve), else
+                // the tiles holding A_bk's nonzero columns (the only ones G A_bk^T reads)
+                int gc = 0;
+                for (int c = 0; c < NWP; ++c) gc |= ((rm.kb >> (4 * c)) & 15 ? 1 : 0) << c;
+                if (tk.a == tk.b) gc = (1 << NWP) - 1;
+                // the W_k rows to load: G's product runs over every chunk from ka's lowest to its highest
+                // (mfma_spread), so the chunks between them are loaded too (their A_ak columns are exact
+                // zeros, which must meet loaded, finite W_k rows)
+                int load = rm.ka;
+                if (load) {
+                    const int lo = __builtin_ctz((unsigned)load), hi = 32 - __builtin_clz((unsigned)load);
+                    load = (int)(((1u << hi) - 1u) & ~((1u << lo) - 1u));
+                }
+                imask.push_back(ItemMask{rm.ra | rm.rb << 4 | gc << 8 | (inv ? padp[tk.a] << 12 : 0) | tpre[t] << 16,
+                                         load, rm.kb, 0});
+                if (item_src) item_src->push_back(s);
+            }
+        }
+}
+
 }  // namespace ba
 }  // namespace sfmx
 
@@ -442,4 +494,39 @@ extern "C" int sfmx_ba_plan(int32_t n_cams, const uint8_t* adj, int32_t order, s
                 r[4] = p.tasks[t].s0; r[5] = p.tasks[t].s1;
             }
     return SFMX_OK;
+}
+
+extern "C" int sfmx_ba_plan_masks(int32_t n_cams, const uint8_t* adj, int32_t order, int32_t* src_mask, int32_t src_cap,
+                                  int32_t* pad_panels, int32_t tiles_cap, int32_t* item_mask, int32_t* item_src,
+                                  int32_t items_cap) {
+    if (n_cams < 0 || (n_cams > 0 && !adj) || order < -1 || order > 4) {
+        sfmx::set_last_error("sfmx_ba_plan_masks: invalid arguments");
+        return SFMX_EINVAL;
+    }
+    const int C = n_cams;
+    std::vector<char> a((size_t)C * C);
+    for (size_t i = 0; i < a.size(); ++i) a[i] = adj[i] != 0;
+    sfmx::ba::FactorPlan p;
+    sfmx::ba::make_plan(C, a, order, p);
+    std::vector<int> tpre, isrc;
+    std::vector<sfmx::ba::ItemMask> im;
+    sfmx::ba::item_masks(p, tpre, im, &isrc);
+    const int n = (int)im.size();
+    if ((src_mask && src_cap < (int)p.src.size()) || (pad_panels && tiles_cap < p.T) ||
+        ((item_mask || item_src) && items_cap < n)) {
+        sfmx::set_last_error("sfmx_ba_plan_masks: output capacity too small");
+        return SFMX_ECAPACITY;
+    }
+    if (src_mask)
+        for (size_t s = 0; s < p.src.size(); ++s) {
+            const sfmx::ba::RowMask& m = p.src_mask[s];
+            src_mask[4 * s] = m.ra; src_mask[4 * s + 1] = m.rb; src_mask[4 * s + 2] = m.ka; src_mask[4 * s + 3] = m.kb;
+        }
+    if (pad_panels) for (int t = 0; t < p.T; ++t) pad_panels[t] = p.pad_panels[t];
+    if (item_mask)
+        for (int i = 0; i < n; ++i) {
+            item_mask[4 * i] = im[i].x; item_mask[4 * i + 1] = im[i].y; item_mask[4 * i + 2] = im[i].z; item_mask[4 * i + 3] = im[i].w;
+        }
+    if (item_src) for (int i = 0; i < n; ++i) item_src[i] = isrc[i];
+    return n;
 }

@@ -36,6 +36,11 @@ struct PlanTask { int a, b, s0, s1; };   // destination tile (a, b), a >= b; sou
 // 16-row strips of A_ak (ra) and A_bk (rb) and the 4-column chunks of their columns (ka, kb) that
 // can be nonzero; per tile the 16-row panels that are identity padding (bit q = rows 16q .. 16q + 15).
 struct RowMask { int ra, rb, ka, kb; };
+// What chol_factor reads per item (item_masks; uploaded as one int4 each): x = ra | rb << 4 | G's column
+// tiles << 8 | the inverted tile's padding panels << 12 | the pre-swept panels << 16, y = the W_k row
+// chunks it loads (ka with every chunk between its lowest and highest one set: the product runs over
+// that whole range), z = kb, w = 0.
+struct ItemMask { int x, y, z, w; };
 
 struct FactorPlan {
     int C = 0, npad = 0, T = 0, order = 0;          // order: 0 natural, 1 nested dissection
@@ -61,14 +66,23 @@ struct FactorPlan {
     std::vector<int> pad_panels;                    // per tile
 };
 
-// adj: C x C row-major 0/1, the global camera co-visibility (symmetric; the diagonal is ignored).
+// adj: C x C row-major 0/1, the global camera co-visibility (either triangle of a pair may be set: the
+// plan and its masks are those of the symmetric closure; the diagonal is ignored).
 // order_mode: -1 automatic (latency model), 0 natural, 1 nested dissection (leaf_tiles chosen by
 // the model), 2/3/4 nested dissection with leaves of 1/2/4 tiles.
 void make_plan(int C, const std::vector<char>& adj, int order_mode, FactorPlan& out);
 
 // (computed at the end of make_plan into P.src_mask / P.pad_panels)
+// adj must be symmetric here (make_plan passes the symmetric closure).
 void row_masks(const FactorPlan& P, const std::vector<char>& adj, std::vector<RowMask>& src_mask,
                std::vector<int>& pad_panels);
+
+// chol_factor's items in launch order (the leaves, then per level every task's sources: item = one src
+// entry) with the masks each reads, from P.src_mask / P.pad_panels; tpre: per task, the panels an
+// inverting one-source diagonal task sweeps before its update (every factorization form).
+// item_src (optional): per item its src entry, -1 for a leaf.
+void item_masks(const FactorPlan& P, std::vector<int>& tpre, std::vector<ItemMask>& imask,
+                std::vector<int>* item_src = nullptr);
 
 }  // namespace ba
 }  // namespace sfmx

@@ -627,7 +627,7 @@ int ensure_plan(sfmx_ba_ctx* c) {
     // between solves really runs each form
     std::string form;
     for (const char* k : {"SFMX_BA_ORDER", "SFMX_BA_BACK", "SFMX_BA_SPEC", "SFMX_BA_DAG", "SFMX_BA_DAG_TIMEOUT", "SFMX_BA_WIDE",
-                          "SFMX_BA_SPLIT"}) {
+                          "SFMX_BA_SPLIT", "SFMX_BA_POISON"}) {
         const char* v = SFMX_DIAG_ENV(k);
         form += std::string(k) + "=" + (v ? v : "") + ";";
     }
@@ -731,24 +731,18 @@ int ensure_plan(sfmx_ba_ctx* c) {
         for (int l = 0; l < pl.height; ++l)
             for (int t = pl.task_start[l]; t < pl.task_start[l + 1]; ++t)
                 vfin[vid(pl.tasks[t].a, pl.tasks[t].b)] += 1 + ((t - pl.task_start[l]) < pl.ninv[l] ? 1 : 0);
-        std::vector<int4> items, need, imask;
-        const std::vector<sfmx::ba::RowMask>& smask = pl.src_mask;   // (made with the plan)
-        const std::vector<int>& padp = pl.pad_panels;
-        // r06: per task, the panels an inverting one-source task sweeps before its update (the ones
-        // outside A_ak's row strips and not padding); every factorization form uses the same order
-        std::vector<int> tpre(std::max<size_t>(pl.tasks.size(), 1), 0);
-        for (int l = 0; l < pl.height; ++l)
-            for (int t = pl.task_start[l]; t < pl.task_start[l + 1]; ++t) {
-                const auto& tk = pl.tasks[t];
-                const bool inv = (t - pl.task_start[l]) < pl.ninv[l];
-                if (inv && tk.a == tk.b && tk.s1 - tk.s0 == 1)
-                    tpre[t] = ~smask[tk.s0].ra & ((1 << NW) - 1) & ~padp[tk.a];
-            }
+        std::vector<int4> items, need;
+        // r06: the row masks of every item and, per task, the panels an inverting one-source task sweeps
+        // before its update (every factorization form uses the same order): ba_plan.cpp item_masks, in
+        // the item order of the loops below; uploaded as they come
+        std::vector<int> tpre;
+        std::vector<sfmx::ba::ItemMask> imask;
+        static_assert(sizeof(sfmx::ba::ItemMask) == sizeof(int4), "an item's masks upload as one int4");
+        sfmx::ba::item_masks(pl, tpre, imask);
         up.add(c->tpre, tpre, true);
         for (int k : pl.leaves) {
             items.push_back(make_int4(k, -1, 0, 0));
             need.push_back(make_int4(0, 0, 0, 0));
-            imask.push_back(make_int4(padp[k] << 12, 0, 0, 0));
             vcnt[vid(k, k)] = 2;
         }
         int dslots = 0;
@@ -762,16 +756,6 @@ int ensure_plan(sfmx_ba_ctx* c) {
                     dag_ok = dag_ok && k < tk.b && vcnt[vid(tk.a, k)] == vfin[vid(tk.a, k)] &&
                              vcnt[vid(tk.b, k)] == vfin[vid(tk.b, k)] && vcnt[vid(k, k)] == vfin[vid(k, k)];
                     items.push_back(make_int4(t, tk.s0 + j, n == 1 ? 0 : dslots + j, n | inv << 16));
-                    {   // G's column tiles: all for a diagonal task (G^T is stored for the back solve), else
-                        // the tiles holding A_bk's nonzero columns (the only ones G A_bk^T reads)
-                        const sfmx::ba::RowMask& rm = smask[tk.s0 + j];
-                        int gc = 0;
-                        for (int c = 0; c < NW; ++c) gc |= ((rm.kb >> (4 * c)) & 15 ? 1 : 0) << c;
-                        if (tk.a == tk.b) gc = (1 << NW) - 1;
-                        const int pre = tpre[t];
-                        imask.push_back(make_int4(rm.ra | rm.rb << 4 | gc << 8 | (inv ? padp[tk.a] << 12 : 0) | pre << 16,
-                                                  rm.ka, rm.kb, 0));
-                    }
                     need.push_back(make_int4(vfin[vid(tk.a, k)], tk.a == tk.b ? 0 : vfin[vid(tk.b, k)], vfin[vid(k, k)],
                                              vcnt[vid(tk.a, tk.b)]));
                 }
@@ -789,6 +773,14 @@ int ensure_plan(sfmx_ba_ctx* c) {
         HIPCHK(hipMemsetAsync(c->dctr.p, 0, c->dctr.bytes, st));
         const char* ed = SFMX_DIAG_ENV("SFMX_BA_DAG");
         c->dag = dag_ok && !(ed && ed[0] == '0');
+#ifdef SFMX_DIAG
+        {   // SFMX_BA_POISON=1 (ba_chol.hpp g_chol_poison): on the solve's stream, before any chol_factor of this plan
+            const char* ep = SFMX_DIAG_ENV("SFMX_BA_POISON");
+            const int poison = ep && ep[0] == '1';
+            HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(sfmx::ba::g_chol_poison), &poison, sizeof(int), 0, hipMemcpyHostToDevice, st));
+            HIPCHK(hipStreamSynchronize(st));   // (the source is this block's local)
+        }
+#endif
         if (const char* et = SFMX_DIAG_ENV("SFMX_BA_DAG_TIMEOUT")) c->dag_timeout = std::atoll(et);   // recovery test
         max_slots = std::max(max_slots, dslots);
         const int tpo = std::max(1, NTH / (NB * RW)), opt = NB * RW / (NTH / tpo);

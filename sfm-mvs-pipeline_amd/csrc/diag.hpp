@@ -16,6 +16,11 @@
 // launch sequences only a non-product route reaches are in match_diag.hip,
 // which is empty without -DSFMX_DIAG; kernel templates both libraries
 // instantiate are in match_device.hpp.
+//
+// SFMX_BA_POISON=1 (diagnostic build, read with the BA plan's form switches in ba_solver.hip ensure_plan):
+// chol_factor fills the LDS buffer of W_k with quiet NaNs before it loads the W_k rows its masks name
+// (ba_chol.hpp g_chol_poison), so a product over a row the item never loaded fails every time instead of
+// depending on what the previous workgroup left there.
 #pragma once
 
 // SFMX_SIFT_VARIANT value (diagnostic build) of the list path with the exact int8 screen and the subset

@@ -194,6 +194,9 @@ PROTOTYPES = {
     "sfmx_ba_jacobian": (C.c_int, [_P(sfmx_ba_problem), C.c_int32, _vp, _vp, _vp, _vp]),
     "sfmx_ba_plan": (C.c_int, [C.c_int32, _vp, C.c_int32, _P(sfmx_ba_plan_info), _i32p, _i32p, C.c_int32, _i32p,
                                C.c_int32, _i32p, C.c_int32]),
+    "sfmx_ba_plan_masks": (C.c_int, [C.c_int32, _vp, C.c_int32, _i32p, C.c_int32, _i32p, C.c_int32, _i32p, _i32p,
+                                     C.c_int32]),
+    "sfmx_ba_debug_chol_items": (C.c_int, [_vp, _vp, C.c_int32]),   # diagnostic library only
     "sfmx_pose_to_ceres": (C.c_int, [_P(C.c_double), _P(C.c_double)]),
     "sfmx_pose_from_ceres": (C.c_int, [_P(C.c_double), _P(C.c_double)]),
     "sfmx_homography_ratios": (C.c_int, [_P(_vp), _i32p, C.c_int32, _i32p, _i32p, C.c_int32, _vp, _vp, C.c_double,

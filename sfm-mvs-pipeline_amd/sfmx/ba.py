@@ -249,6 +249,19 @@ def factor_plan(adj: np.ndarray, order: int = ORDER_AUTO) -> dict:
                            i32(tasks), len(tasks), i32(src), len(src)), "sfmx_ba_plan")
     out = {f: getattr(info, f) for f, _ in info._fields_}
     out.update(camrow=camrow[:n], leaves=leaves[:info.leaves], tasks=tasks[:info.tasks], src=src[:info.src])
+    # the row masks of the same plan (sfmx_ba_plan_masks): per src entry (ra, rb, ka, kb), per tile its
+    # padding panels, per chol_factor item the uploaded words (x, y, z, w) and its src entry (-1: a leaf)
+    ni = info.leaves + info.src
+    src_mask = np.zeros((max(info.src, 1), 4), np.int32)
+    pad_panels = np.zeros(max(info.tiles, 1), np.int32)
+    item_mask = np.zeros((max(ni, 1), 4), np.int32)
+    item_src = np.zeros(max(ni, 1), np.int32)
+    got = check(lib.sfmx_ba_plan_masks(n, adj.ctypes.data, order, i32(src_mask), len(src_mask), i32(pad_panels),
+                                       len(pad_panels), i32(item_mask), i32(item_src), len(item_mask)),
+                "sfmx_ba_plan_masks")
+    assert got == ni, (got, ni)
+    out.update(src_mask=src_mask[:info.src], pad_panels=pad_panels[:info.tiles], item_mask=item_mask[:ni],
+               item_src=item_src[:ni])
     return out
 
 
