@@ -4,7 +4,8 @@ lib/libsfmx.so reads no environment variable: its kernels are the shipped forms
 only.  The kernel variants, the alternative BA factorization forms and the
 timing probes live in lib/libsfmx_diag.so (`make diag`, -DSFMX_DIAG,
 csrc/diag.hpp), which reads SFMX_SIFT_VARIANT, SFMX_SIFT_P2, SFMX_ORB_VARIANT,
-SFMX_BA_ORDER / _BACK / _SPLIT / _DAG / _SPEC, SFMX_SIFT_SMALL[_PX].
+SFMX_BA_ORDER / _BACK / _SPLIT / _DAG / _SPEC, SFMX_SIFT_SMALL[_PX],
+SFMX_SIFT_XCD[_EXTREMA], SFMX_SIFT_EX_ROWS.
 
 `diagnostic(**env)` loads that library next to the product one (both are
 RTLD_LOCAL, so each resolves its own symbols and registers its own kernels),

@@ -3,6 +3,7 @@ behaviour of the restatement of OpenCV 4.5.1 SIFT::detectAndCompute
 (oracle/sift_oracle.cpp) on synthetic images.  Parity against OpenCV itself
 is unpinned (OpenCV is not available here)."""
 import numpy as np
+import pytest
 
 from oracle import oracle
 import sift_cases
@@ -19,6 +20,68 @@ def test_single_blob_found_at_its_centre():
     # blob sigma 6 -> keypoint size ~ 2 * sqrt(2) * 6 (the DoG scale of a Gaussian blob)
     assert 8 < best["size"] < 30
     assert d.shape == (len(k), 128) and np.all(d == np.rint(d)) and d.min() >= 0 and d.max() <= 255
+
+
+@pytest.mark.parametrize("sigma", [1.6, 2.4])
+@pytest.mark.parametrize("L", [1, 2, 3, 4, 5, 6, 8])
+def test_blob_scale_follows_the_layer_count(L, sigma):
+    """An isolated Gaussian blob of standard deviation s keeps s^2 / (s^2 + t^2) of its amplitude after a
+    blur of t, so the DoG between t and k t at its centre peaks at t = s / sqrt(k), k = 2^(1/L): the
+    strongest keypoint has size 2 s / 2^(1/(2L)) (2 t: SIFT's size is twice the scale).  The ratio
+    size / s runs from 1.41 (L = 1) to 1.91 (L = 8), so a scale formula with 3 in L's place misses by tens of
+    percent.  Bound: 3 % (5 % at L = 1, whose single inner layer leaves the parabola fit of the scale
+    offset only coarse samples); seen: at most 1.3 % for L >= 2 and 3.3 % for L = 1 (s = 4, sigma 2.4)."""
+    for s in (4.0, 6.0, 9.0):
+        k, _ = oracle.sift(sift_cases.single_blob_image(s), n_octave_layers=L, sigma=sigma, descriptors=False)
+        assert len(k) >= 1
+        best = k[np.argmax(k["response"])]
+        law = 2 * s / 2 ** (1 / (2 * L))
+        dev = best["size"] / law - 1
+        print(f"L={L} sigma={sigma} s={s}: n={len(k)} x={best['x']:.2f} y={best['y']:.2f} size={best['size']:.3f} "
+              f"law={law:.3f} dev={100 * dev:+.2f}%")
+        assert abs(best["x"] - 70.3) < 1.0 and abs(best["y"] - 41.6) < 1.0
+        assert abs(dev) < (0.05 if L == 1 else 0.03)
+
+
+def _rows(k, d):
+    return {k[i].tobytes(): d[i].tobytes() for i in range(len(k))}
+
+
+def _assert_filter_chain(results, counts):
+    """results: loosest-last list of (keypoints, descriptors); each must be a subset of the next, with
+    equal descriptor rows on the common keypoints, and the counts those recorded for the oracle."""
+    assert [len(k) for k, _ in results] == counts
+    for (ka, da), (kb, db) in zip(results, results[1:]):
+        a, b = _rows(ka, da), _rows(kb, db)
+        assert len(a) == len(ka) and len(b) == len(kb)
+        assert set(a) <= set(b)
+        assert all(b[key] == row for key, row in a.items())
+
+
+def test_thresholds_only_filter():
+    """edgeThreshold and contrastThreshold decide which refined extrema are kept and touch nothing else
+    (up to the extrema pre-filter floor(0.5 c / L * 255), which is monotone in c too): with nfeatures = 0
+    the keypoint rows at a stricter setting are, byte for byte, a subset of those at a looser one, with
+    the same descriptor rows.  The counts differ along each chain, so each parameter is seen to act."""
+    img = sift_cases.blob_image(150, 190, n_blobs=100, seed=5)
+    _assert_filter_chain([oracle.sift(img, contrast_threshold=0.04, edge_threshold=e) for e in (1.2, 2, 3, 5, 10, 50)],
+                         [6, 20, 30, 35, 35, 35])
+    _assert_filter_chain([oracle.sift(img, contrast_threshold=c) for c in (0.2, 0.09, 0.04, 0.02, 0)],
+                         [0, 17, 35, 46, 87])
+
+
+def test_row_pitch_is_honoured():
+    """orc_sift on rows W + 5 bytes apart (random bytes in the padding) equals the contiguous call."""
+    img = sift_cases.blob_image(90, 110, n_blobs=60, seed=8)
+    big, view = sift_cases.padded(img, left=0, right=5)
+    assert view.strides[0] == img.shape[1] + 5 and not view.flags["C_CONTIGUOUS"]
+    ek, ed = oracle.sift(img, contrast_threshold=0.04)
+    assert len(ek) > 10
+    k = np.zeros(len(ek) + 8, oracle.KEYPOINT_DTYPE)
+    d = np.zeros((len(ek) + 8, 128), np.float32)
+    n = oracle.lib.orc_sift(view.ctypes.data, img.shape[1], img.shape[0], view.strides[0], 0, 3, 0.04, 10.0, 1.6,
+                            k.ctypes.data, d.ctypes.data, len(k))
+    assert n == len(ek) and k[:n].tobytes() == ek.tobytes() and np.array_equal(d[:n], ed)
 
 
 def test_outputs_sorted_unique_and_retain_best():
