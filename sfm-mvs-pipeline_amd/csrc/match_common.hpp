@@ -41,6 +41,16 @@ inline int arena_words(int n_pairs) { return 2 * n_pairs + ARENA_FIXED; }
 // (sift_subset_kernel does not gather it) and not two bits (sift_finish_kernel reads the slot's own two keys).
 constexpr int32_t QMASK_FULL_ROUTE = 1 << 16;
 
+// The matcher's last-arriver scratch, int32 words (matcher.cpp ensure_scratch; DESIGN 5 "last arriver"): tickets
+// that are zero between kernels (zeroed when the buffer is allocated, set back to zero by the workgroup that reads
+// the last value), and the prepare kernel's per-workgroup maxima, which are written before they are read.
+//   [SCRATCH_FINISH]            sift_finish_kernel: workgroups done (the last one scans the counts)
+//   [SCRATCH_PREP]              prep_l2_batch_kernel: images done (the last one publishes the flags)
+//   [SCRATCH_IMG + i]           prep_l2_batch_kernel: workgroups of image i done, i < n_flags (a multiple of 64)
+//   [SCRATCH_IMG + n_flags ..)  int2 (emax, amax) of workgroup (image, blockIdx.x): [n][grid x]
+constexpr int SCRATCH_FINISH = 0, SCRATCH_PREP = 1, SCRATCH_IMG = 64;
+inline int64_t scratch_words(int64_t n_flags, int64_t n, int64_t grid_x) { return SCRATCH_IMG + n_flags + 2 * n * grid_x; }
+
 struct ImgDev {
     int32_t rows;       // real descriptor rows (Nq or Nt)
     int32_t rows_pad;   // multiple of ROW_ALIGN
@@ -172,18 +182,25 @@ struct MatchBufs {
     int32_t* keep;
     int64_t* offsets;
     DMatchDev* out;
+    int32_t* scratch;              // the last-arriver tickets (SCRATCH_* above)
 };
 
 // Launchers of match_kernels.hip (both libraries).
+struct FlagHandoff {               // where the prepare kernel's last workgroup publishes the integrality flags
+    int32_t* dst;                  // host-coherent: one word per image
+    unsigned* seq;                 // host-coherent sequence word, release-stored behind the flags
+    unsigned value;                // the value the host waits for
+};
+int prep_l2_grid_x(int max_rows_pad);
 hipError_t launch_prep_l2_batch(const PrepImg*, int, int, int8_t*, int32_t*, int32_t*, int32_t*, int32_t*, uint32_t*, float*,
-                                int2*, int32_t*, hipStream_t);
-hipError_t launch_publish_flags(const int32_t*, int, int32_t*, unsigned*, unsigned, hipStream_t);
+                                int2*, int32_t*, int32_t* scratch, int n_flags, const FlagHandoff&, hipStream_t);
 hipError_t launch_prep_f32(const float*, int, int, int, float*, hipStream_t);
 hipError_t launch_prep_hamming_fp4(const uint8_t*, int, int, int, uint8_t*, int32_t*, hipStream_t);
 hipError_t launch_selftest_sqrt(int64_t, uint32_t*, hipStream_t);
 hipError_t launch_sift_product(const MatchBufs& b, int n_work, int n_pairs, double ratio, int full_row_grid, hipStream_t st,
                                hipEvent_t ev_screen);
-hipError_t launch_sift_full_rows(const MatchBufs& b, int n_work, int n_pairs, double ratio, int full_row_grid, hipStream_t st);
+hipError_t launch_sift_full_rows(const MatchBufs& b, int n_work, int n_pairs, double ratio, int full_row_grid, hipStream_t st,
+                                 bool compact = true);
 hipError_t launch_orb_product(const MatchBufs& b, int n_work, int n_pairs, double ratio, hipStream_t st, hipEvent_t ev_screen);
 hipError_t launch_orb_pass2(const MatchBufs& b, const int32_t* porder, int np, const int32_t* settle_order, double ratio,
                             hipStream_t st);

@@ -642,13 +642,22 @@ constexpr int SIFT_RIDE_MAX = 32;
 //
 // Result: a certified slot has one writer, which stores (k1, k2) as one 16-B word over the slot's `top2`
 // pair (sift_finish_kernel clamps s2 for a one-bit mask); a rider takes sift_subset_kernel's three atomics.
+//
+// Work list of the full-row launch behind this kernel (work2 not null): workgroup 0 builds it from qcount2 before
+// its own item (compact_work_block, the body of compact_work_kernel), whatever that item turns out to be.  The
+// screen has finished, so the counts are final, and the list's only reader is the next kernel on the stream.
+template <int ISH, int THREADS>
+__device__ __forceinline__ void compact_work_block(const int32_t* __restrict__ porder, int n_pairs,
+                                                   const int32_t* __restrict__ qcount, WorkItem* __restrict__ work2,
+                                                   int32_t* __restrict__ work2_n, int ride, int* wsum);
 template <int QTMAX>
 __global__ __launch_bounds__(256, 4)
 void sift_rows_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restrict__ imgs,
                       const int8_t* __restrict__ desc8, const int32_t* __restrict__ norm,
                       const int32_t* __restrict__ qlist, const int32_t* __restrict__ qmask,
                       const int32_t* __restrict__ qcount, const int32_t* __restrict__ qcount2,
-                      const int32_t* __restrict__ porder, unsigned long long* __restrict__ top2) {
+                      const int32_t* __restrict__ porder, unsigned long long* __restrict__ top2,
+                      WorkItem* __restrict__ work2 = nullptr, int32_t* __restrict__ work2_n = nullptr, int n_pairs = 0) {
     constexpr int WIN = 1024;                 // forwarded-query window scanned per round
     constexpr int EPT = WIN / 256;            // window entries per thread
     constexpr int RIDER = 1 << 30;
@@ -664,6 +673,8 @@ void sift_rows_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restric
 
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, l32 = lane & 31;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: the subset and all that follows from it
+    if (work2 && blockIdx.x == 0)             // (pool: free until the first window; the function ends with a barrier)
+        compact_work_block<7, 256>(porder, n_pairs, qcount2, work2, work2_n, SIFT_RIDE_MAX, pool);
     const int item = xcd_remap(blockIdx.x, gridDim.x);
     const int pi = porder[item >> 2], G = item & 3, r = 4 * G + wid;
     const int cnt = qcount[pi];
@@ -852,15 +863,15 @@ void sift_rows_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restric
 
 // Pass-2 work list: ceil(qcount[p] / 512) items per pair, pairs in the host's
 // order (sorted by train image, so XCD-contiguous items share train rows).
-// One 1024-thread block; each thread owns a contiguous run of pairs.
+// One workgroup of THREADS threads; each thread owns a contiguous run of pairs.
 // A pair with at most `ride` queries gets no item (its queries ride the subset kernel; 0: every pair with a query).
-template <int ISH>   // queries per pass-2 item = 1 << ISH
-__global__ __launch_bounds__(1024)
-void compact_work_kernel(const int32_t* __restrict__ porder, int n_pairs, const int32_t* __restrict__ qcount,
-                         WorkItem* __restrict__ work2, int32_t* __restrict__ work2_n, int ride = 0) {
-    __shared__ int wsum[16];
+// wsum: THREADS / 64 words of the caller's LDS, free again on return.
+template <int ISH, int THREADS>   // queries per pass-2 item = 1 << ISH
+__device__ __forceinline__ void compact_work_block(const int32_t* __restrict__ porder, int n_pairs,
+                                                   const int32_t* __restrict__ qcount, WorkItem* __restrict__ work2,
+                                                   int32_t* __restrict__ work2_n, int ride, int* wsum) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int per = (n_pairs + 1023) / 1024, p0 = min(tid * per, n_pairs), p1 = min(p0 + per, n_pairs);
+    const int per = (n_pairs + THREADS - 1) / THREADS, p0 = min(tid * per, n_pairs), p1 = min(p0 + per, n_pairs);
     int mine = 0;
     auto items = [&](int c) { return c > ride ? (c + (1 << ISH) - 1) >> ISH : 0; };
     for (int i = p0; i < p1; ++i) mine += items(qcount[porder[i]]);
@@ -878,7 +889,15 @@ void compact_work_kernel(const int32_t* __restrict__ porder, int n_pairs, const 
         const int p = porder[i], n = items(qcount[p]);
         for (int k = 0; k < n; ++k) work2[at++] = WorkItem{p, k << ISH};
     }
-    if (tid == 1023) *work2_n = base + incl;
+    if (tid == THREADS - 1) *work2_n = base + incl;
+    __syncthreads();
+}
+template <int ISH>
+__global__ __launch_bounds__(1024)
+void compact_work_kernel(const int32_t* __restrict__ porder, int n_pairs, const int32_t* __restrict__ qcount,
+                         WorkItem* __restrict__ work2, int32_t* __restrict__ work2_n, int ride = 0) {
+    __shared__ int wsum[16];
+    compact_work_block<ISH, 1024>(porder, n_pairs, qcount, work2, work2_n, ride, wsum);
 }
 
 // Exact path for queries whose best-2 falls in the float-sqrt collision range:

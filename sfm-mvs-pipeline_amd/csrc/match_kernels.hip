@@ -44,6 +44,20 @@
 namespace sfmx {
 
 // ---------------------------------------------------------------------------
+// Last arrivers: a workgroup hands a few words to whichever workgroup of the grid finishes last.
+// A device-scope release fence in front of the ticket writes the XCD's whole L2 back, once per workgroup
+// (prep_l2_batch_kernel 140 -> 460-490 us, sift_finish_kernel 17 -> 46 us with it, profiles/folds_ab_step.txt).
+// So the handed-over words, and only they, move as device-scope atomics, which are performed at the point that is
+// coherent for every XCD: the writer's returning atomics have been performed when their values are back
+// (handed_over waits for them), its ticket is issued after that, and the last arriver issues its device-scope
+// atomic loads after its own ticket has returned.  Nothing else a workgroup wrote is read before the kernel ends.
+__device__ __forceinline__ void hand_over(unsigned long long* p, unsigned long long v) {
+    const unsigned long long old = atomicExch(p, v);
+    asm volatile("" ::"v"(old));   // the returning form: complete when the value is back
+}
+__device__ __forceinline__ void handed_over() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// ---------------------------------------------------------------------------
 // prep: float SIFT rows -> int8 a' = a - 128, ||a'||^2, chunk keys, integrality.
 // 32 threads per row (float4 each); pad rows are written as zeros.
 // The FP6 screen's per-row operands (sift_fp6.hpp), written by the batched prep beside the int8 ones.
@@ -59,36 +73,92 @@ __device__ __forceinline__ int2 prep_l2_row(const float* __restrict__ src, int r
 // All images of a set_images call in one launch: blockIdx.y = image (table in HBM).
 constexpr int PREP_ROWS = 64;   // rows per workgroup of the batched prep
 static_assert(ROW_ALIGN % PREP_ROWS == 0 && PREP_ROWS % 8 == 0, "whole 8-row steps, no partial workgroup");
+//
+// The kernel finishes its own job (no fill in front, no publishing kernel behind): last arrivers, DESIGN 5.
+// One thread of a workgroup hands its (emax, amax) over in its own slot of `part` and its integrality finding in
+// the image's flag (hand_over above), and then takes the image's ticket.  Whoever draws the image's last ticket
+// reduces the image's slots into imax[2 i], imax[2 i + 1] (plain stores: no zeroed word, no atomicMax), puts the
+// ticket back to 0 and takes the global ticket; whoever draws the last of those copies the n flags to the host
+// words, release-stores the sequence word at system scope and leaves flags and the ticket at 0 for the next call.
+// Nothing waits.  Image i's ticket counts max(rows_pad / PREP_ROWS, 1) workgroups, computed here from rows_pad:
+// a workgroup past its image's rows_pad leaves at once and takes no ticket, except workgroup 0 of an image
+// without rows, which carries that image's zeros.  What a last arriver reads of other workgroups (slots, flags)
+// it reads with device-scope atomics issued behind its own ticket, never through its L2's cached lines.
 __global__ void prep_l2_batch_kernel(const PrepImg* __restrict__ tab, int8_t* __restrict__ desc8,
                                      int32_t* __restrict__ norm, int32_t* __restrict__ keyc,
                                      int32_t* __restrict__ keyc2, int32_t* __restrict__ flags, Fp6Rows f6,
-                                     int32_t* __restrict__ imax) {
+                                     int32_t* __restrict__ imax, int32_t* __restrict__ scratch, int n_flags,
+                                     FlagHandoff pub) {
     const PrepImg t = tab[blockIdx.y];
+    if (blockIdx.x != 0 && (int)blockIdx.x * PREP_ROWS >= t.rows_pad) return;
+    __shared__ int wmax[2][PREP_ROWS / 8];
+    __shared__ int s_bad, s_last;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
     const Fp6Rows f6i{f6.desc6 + t.row0 * fp6::ROW_WORDS, f6.keyf + t.row0, f6.ne + t.row0};
     int emax = 0, amax = 0;   // the image's largest |e|^2 and |a|^2 over this workgroup's rows
     // PREP_ROWS rows per workgroup, 8 at a time (rows_pad is a multiple of PREP_ROWS)
-    for (int r = blockIdx.x * PREP_ROWS + (threadIdx.x >> 5); r < min((int)(blockIdx.x + 1) * PREP_ROWS, t.rows_pad);
+    for (int r = blockIdx.x * PREP_ROWS + (tid >> 5); r < min((int)(blockIdx.x + 1) * PREP_ROWS, t.rows_pad);
          r += blockDim.x >> 5) {
         const int2 em = prep_l2_row(t.src, r, t.rows, t.cols, desc8 + t.row0 * SIFT_DIM, norm + t.row0, keyc + t.row0,
-                                    keyc2 + t.row0, flags + blockIdx.y, &f6i);
+                                    keyc2 + t.row0, &s_bad, &f6i);
         emax = max(emax, em.x);
         amax = max(amax, em.y);
     }
-    // One pair of atomics per workgroup at most, and only where it raises the image's maximum (imax is zero
-    // before the launch): every image's words share a few cache lines, and unconditional atomics from each
-    // wave serialised there (prep 283 -> 158 us on 50 x 8192 rows with this guard).
-    __shared__ int wmax[2][PREP_ROWS / 8];
     for (int o = 32; o > 0; o >>= 1) {
         emax = max(emax, __shfl_xor(emax, o));
         amax = max(amax, __shfl_xor(amax, o));
     }
-    if ((threadIdx.x & 63) == 0) { wmax[0][threadIdx.x >> 6] = emax; wmax[1][threadIdx.x >> 6] = amax; }
+    if ((tid & 63) == 0) { wmax[0][tid >> 6] = emax; wmax[1][tid >> 6] = amax; }
     __syncthreads();
-    if (threadIdx.x < 2) {
-        int v = 0;
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) v = max(v, wmax[threadIdx.x][i]);
-        int32_t* p = imax + 2 * blockIdx.y + threadIdx.x;
-        if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
+    const int need = max(t.rows_pad / PREP_ROWS, 1);
+    unsigned long long* part = reinterpret_cast<unsigned long long*>(scratch + SCRATCH_IMG + n_flags) +
+                               (int64_t)blockIdx.y * gridDim.x;
+    if (tid == 0) {
+        int e = 0, a = 0;
+        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) { e = max(e, wmax[0][i]); a = max(a, wmax[1][i]); }
+        hand_over(part + blockIdx.x, (unsigned long long)(unsigned)e | ((unsigned long long)(unsigned)a << 32));
+        if (s_bad) {
+            const int old = atomicOr(flags + blockIdx.y, 1);
+            asm volatile("" ::"v"(old));
+        }
+        handed_over();
+        s_last = atomicAdd(scratch + SCRATCH_IMG + blockIdx.y, 1) == need - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    // the image's last workgroup: every slot of the image has been performed
+    emax = amax = 0;
+    for (int i = tid; i < need; i += blockDim.x) {
+        const unsigned long long p = __hip_atomic_load(part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        emax = max(emax, (int)(unsigned)p);
+        amax = max(amax, (int)(unsigned)(p >> 32));
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        emax = max(emax, __shfl_xor(emax, o));
+        amax = max(amax, __shfl_xor(amax, o));
+    }
+    if ((tid & 63) == 0) { wmax[0][tid >> 6] = emax; wmax[1][tid >> 6] = amax; }
+    __syncthreads();
+    if (tid == 0) {
+        int e = 0, a = 0;
+        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) { e = max(e, wmax[0][i]); a = max(a, wmax[1][i]); }
+        imax[2 * blockIdx.y] = e;
+        imax[2 * blockIdx.y + 1] = a;
+        __hip_atomic_store(scratch + SCRATCH_IMG + blockIdx.y, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // (the image's flag was performed before any of its tickets; imax and the ticket's reset wait for no reader here)
+        s_last = atomicAdd(scratch + SCRATCH_PREP, 1) == (int)gridDim.y - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    // the last image's last workgroup: every flag is final
+    for (int i = tid; i < (int)gridDim.y; i += blockDim.x) pub.dst[i] = atomicExch(flags + i, 0);
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) {
+        __hip_atomic_store(scratch + SCRATCH_PREP, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(pub.seq, pub.value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 // -> (|e|^2, |a|^2) of the row's FP6 form (0, 0 for a pad row or without f6).
@@ -189,28 +259,19 @@ __global__ void prep_hamming_fp4_kernel(const uint8_t* __restrict__ src, int row
     }
 }
 
-// imax[2 i], imax[2 i + 1]: image i's largest |e|^2 and |a|^2 (zero before the launch).
+// imax[2 i], imax[2 i + 1]: image i's largest |e|^2 and |a|^2.  flags[n] and the tickets of `scratch` (n_flags image
+// tickets; scratch_words(n_flags, n, prep_l2_grid_x(max_rows_pad)) words) are zero before the launch and after it.
+// The per-image integrality flags go to pinned, host-coherent memory, then a sequence word with system-scope
+// release: set_images spins on the word instead of a D2H copy + hipStreamSynchronize (whose interrupt-driven
+// wake-up the host would pay once per matching call).  A set of empty images still runs one workgroup per image.
+int prep_l2_grid_x(int max_rows_pad) { return std::max((max_rows_pad + PREP_ROWS - 1) / PREP_ROWS, 1); }
 hipError_t launch_prep_l2_batch(const PrepImg* tab, int n, int max_rows_pad, int8_t* desc8, int32_t* norm,
                                 int32_t* keyc, int32_t* keyc2, int32_t* flags, uint32_t* desc6, float* keyf,
-                                int2* ne, int32_t* imax, hipStream_t st) {
-    if (n == 0 || max_rows_pad == 0) return hipSuccess;
-    prep_l2_batch_kernel<<<dim3((unsigned)((max_rows_pad + PREP_ROWS - 1) / PREP_ROWS), (unsigned)n), 256, 0, st>>>(
-        tab, desc8, norm, keyc, keyc2, flags, Fp6Rows{desc6, keyf, ne}, imax);
-    return hipGetLastError();
-}
-// The per-image integrality flags into pinned, host-coherent memory, then a sequence word with
-// system-scope release: set_images spins on the word instead of a D2H copy + hipStreamSynchronize
-// (whose interrupt-driven wake-up the host would pay once per matching call).
-__global__ __launch_bounds__(256)
-void publish_flags_kernel(const int32_t* __restrict__ flags, int n, int32_t* __restrict__ dst, unsigned* __restrict__ seq,
-                          unsigned v) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = flags[i];
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(seq, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-hipError_t launch_publish_flags(const int32_t* flags, int n, int32_t* dst, unsigned* seq, unsigned v, hipStream_t st) {
-    publish_flags_kernel<<<1, 256, 0, st>>>(flags, n, dst, seq, v);
+                                int2* ne, int32_t* imax, int32_t* scratch, int n_flags, const FlagHandoff& pub,
+                                hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    prep_l2_batch_kernel<<<dim3((unsigned)prep_l2_grid_x(max_rows_pad), (unsigned)n), 256, 0, st>>>(
+        tab, desc8, norm, keyc, keyc2, flags, Fp6Rows{desc6, keyf, ne}, imax, scratch, n_flags, pub);
     return hipGetLastError();
 }
 
@@ -476,7 +537,7 @@ __device__ __forceinline__ void dense_count(const unsigned* bits, int* sh, const
         int run = 0, b = 0;
         for (int i = 0; i < 16; ++i) { run += sh[i]; b += sh[16 + i]; }
         if (b) atomicAdd(unsettled, b);
-        counts[p] = run;
+        hand_over(reinterpret_cast<unsigned long long*>(counts + p), (unsigned long long)run);   // (read by sift_finish_kernel's last workgroup)
         keep[p] = run < min_count ? 0 : 1;
     }
 }
@@ -536,17 +597,16 @@ void assemble_kernel(const PairDev* __restrict__ pairs, const ImgDev* __restrict
 // a barrier, one wave each.  Then the distinct filter and the count: with the seen / dup bitsets a
 // train row is matched exactly once iff seen and not dup, so the count is a popcount over the words.
 // A slot pass 2 never wrote counts as unsettled (the run fails in fetch / stats).
-__global__ __launch_bounds__(1024)
-void sift_finish_kernel(const PairRec* __restrict__ recs, const int32_t* __restrict__ qlist,
-                        const int32_t* __restrict__ qmask, const int32_t* __restrict__ qcount,
-                        unsigned long long* __restrict__ top2, const unsigned long long* __restrict__ slot1,
-                        int2* __restrict__ slow_list, int32_t* __restrict__ slow_count,
-                        const int8_t* __restrict__ desc8, const int32_t* __restrict__ norm,
-                        const int32_t* __restrict__ out_idx, double ratio, int distinct, int min_count,
-                        int64_t* __restrict__ counts, int32_t* __restrict__ keep, int32_t* __restrict__ unsettled) {
-    extern __shared__ __attribute__((aligned(16))) unsigned bits[];   // seen | dup bitsets (distinct only)
-    __shared__ int sh[32];
-    __shared__ int s_slow;
+// finish_pair: the workgroup's pair (every path stores counts[pair] from thread 0; the returns are uniform).
+__device__ __forceinline__ void finish_pair(unsigned* bits, int* sh, int& s_slow, const PairRec* __restrict__ recs,
+                                            const int32_t* __restrict__ qlist,
+                                            const int32_t* __restrict__ qmask, const int32_t* __restrict__ qcount,
+                                            unsigned long long* __restrict__ top2, const unsigned long long* __restrict__ slot1,
+                                            int2* __restrict__ slow_list, int32_t* __restrict__ slow_count,
+                                            const int8_t* __restrict__ desc8, const int32_t* __restrict__ norm,
+                                            const int32_t* __restrict__ out_idx, double ratio, int distinct, int min_count,
+                                            int64_t* __restrict__ counts, int32_t* __restrict__ keep,
+                                            int32_t* __restrict__ unsettled) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const PairRec R = recs[blockIdx.x];
     const int nt = R.nt, words = (nt + 31) >> 5;
@@ -558,7 +618,7 @@ void sift_finish_kernel(const PairRec* __restrict__ recs, const int32_t* __restr
     }
     const int cnt = qcount[R.pair];
     if (cnt == 0) {
-        if (tid == 0) { counts[R.pair] = 0; keep[R.pair] = 0 < min_count ? 0 : 1; }
+        if (tid == 0) { hand_over(reinterpret_cast<unsigned long long*>(counts + R.pair), 0); keep[R.pair] = 0 < min_count ? 0 : 1; }
         return;
     }
     if (tid == 0) s_slow = 0;
@@ -634,8 +694,60 @@ void sift_finish_kernel(const PairRec* __restrict__ recs, const int32_t* __restr
         for (int i = 0; i < 16; ++i) { run += sh[i]; b += sh[16 + i]; }
         if (b) atomicAdd(unsettled, b);
         if (n_slow) atomicAdd(slow_count, n_slow);
-        counts[R.pair] = run;
+        hand_over(reinterpret_cast<unsigned long long*>(counts + R.pair), (unsigned long long)run);
         keep[R.pair] = run < min_count ? 0 : 1;
+    }
+}
+// One workgroup per pair record, then the offsets: thread 0, which handed the pair's count over (hand_over), waits for it
+// and takes a ticket; the workgroup that draws the last one (every count is stored and released) scans
+// counts[0, n_pairs) into offsets[0, n_pairs] (scan_offsets_kernel's result) and puts the ticket back to 0.  The
+// counts come from workgroups on other XCDs: device-scope atomic loads issued behind the ticket.  Nothing waits.
+__global__ __launch_bounds__(1024)
+void sift_finish_kernel(const PairRec* __restrict__ recs, const int32_t* __restrict__ qlist,
+                        const int32_t* __restrict__ qmask, const int32_t* __restrict__ qcount,
+                        unsigned long long* __restrict__ top2, const unsigned long long* __restrict__ slot1,
+                        int2* __restrict__ slow_list, int32_t* __restrict__ slow_count,
+                        const int8_t* __restrict__ desc8, const int32_t* __restrict__ norm,
+                        const int32_t* __restrict__ out_idx, double ratio, int distinct, int min_count,
+                        int64_t* __restrict__ counts, int32_t* __restrict__ keep, int32_t* __restrict__ unsettled,
+                        int n_pairs, int64_t* __restrict__ offsets, int32_t* __restrict__ ticket) {
+    extern __shared__ __attribute__((aligned(16))) unsigned bits[];   // seen | dup bitsets (distinct only)
+    __shared__ int sh[32];
+    __shared__ int s_slow, s_last;
+    __shared__ long long wsum[16];
+    finish_pair(bits, sh, s_slow, recs, qlist, qmask, qcount, top2, slot1, slow_list, slow_count, desc8, norm, out_idx, ratio,
+                distinct, min_count, counts, keep, unsettled);
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    if (tid == 0) {
+        handed_over();
+        s_last = atomicAdd(ticket, 1) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    long long run = 0;
+    for (int c0 = 0; c0 < n_pairs; c0 += 1024) {
+        const int i = c0 + tid;
+        const long long v = i < n_pairs ? (long long)__hip_atomic_load(counts + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        long long incl = v;
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long y = __shfl_up(incl, o);
+            if (lane >= o) incl += y;
+        }
+        if (lane == 63) wsum[wid] = incl;
+        __syncthreads();
+        long long base = 0, total = 0;
+        for (int k = 0; k < 16; ++k) {
+            const long long w = wsum[k];
+            base += k < wid ? w : 0;
+            total += w;
+        }
+        if (i < n_pairs) offsets[i] = run + base + incl - v;
+        run += total;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        offsets[n_pairs] = run;
+        __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -778,10 +890,12 @@ constexpr int SIFT_FULL_ROW_SLOTS = 1024;
 // The full-row items of the pairs' second lists (`slot1`, counted behind the arena's qcount2): work2 holds up to
 // n_work << 2 of them and the count stays on the device, so the grid is two resident rounds (or full_row_grid
 // workgroups when that is not 0: MatchRoute), each workgroup looping over the list.
-hipError_t launch_sift_full_rows(const MatchBufs& b, int n_work, int n_pairs, double ratio, int full_row_grid, hipStream_t st) {
+// compact: build the list here (compact_work_kernel); false where the kernel in front has built it (sift_rows_kernel).
+hipError_t launch_sift_full_rows(const MatchBufs& b, int n_work, int n_pairs, double ratio, int full_row_grid, hipStream_t st,
+                                 bool compact) {
     const int32_t* qlist2 = reinterpret_cast<const int32_t*>(b.slot1);
     const int32_t* qcount2 = b.qcount + arena_qcount2(n_pairs);
-    compact_work_kernel<7><<<1, 1024, 0, st>>>(b.porder, n_pairs, qcount2, b.work2, b.work2_n, SIFT_RIDE_MAX);
+    if (compact) compact_work_kernel<7><<<1, 1024, 0, st>>>(b.porder, n_pairs, qcount2, b.work2, b.work2_n, SIFT_RIDE_MAX);
     static const int slots = resident_slots(sift_knn2_kernel<1, 4, 2, 128, false, true, true, true>, 256);
     const int grid = std::min(n_work << 2, full_row_grid > 0 ? full_row_grid : 2 * (slots > 0 ? slots : SIFT_FULL_ROW_SLOTS));
     sift_knn2_kernel<1, 4, 2, 128, false, true, true, true><<<grid, 256, 0, st>>>(
@@ -805,8 +919,8 @@ hipError_t launch_sift_product(const MatchBufs& b, int n_work, int n_pairs, doub
         if (e != hipSuccess) return e;
     }
     sift_rows_kernel<SIFT_ROWS_QT><<<n_pairs * 4, 256, 0, st>>>(b.pairs, b.imgs, b.desc8, b.norm, b.qlist, b.qmask, b.qcount,
-                                                                 qcount2, b.porder, b.top2);
-    return launch_sift_full_rows(b, n_work, n_pairs, ratio, full_row_grid, st);
+                                                                 qcount2, b.porder, b.top2, b.work2, b.work2_n, n_pairs);
+    return launch_sift_full_rows(b, n_work, n_pairs, ratio, full_row_grid, st, false);   // workgroup 0 above built the list
 }
 // ORB pass 2 of np pairs: the subset kernel over the pairs porder[0, np), then the settle, one workgroup per pair
 // (workgroup i: pair settle_order[i], or pair i of the run where settle_order is null).
@@ -850,7 +964,8 @@ hipError_t launch_assemble(const MatchBufs& b, int n_pairs, int distinct, int mi
     return hipGetLastError();
 }
 // The list path's settle + assembly (after the screen and pass 2, and after the fp32 kernel of a mixed run):
-// finish (ev_main is recorded behind it), one scan over every pair's count, write.  One workgroup per record.
+// finish, whose last workgroup scans every pair's count into the offsets (ev_main is recorded behind it), write.
+// One workgroup per record.
 hipError_t launch_finish_lists(const MatchBufs& b, int n_pairs, double ratio, int distinct, int min_count, int max_nq,
                                int max_nt, hipStream_t st, hipEvent_t ev_main) {
     hipError_t e;
@@ -864,10 +979,10 @@ hipError_t launch_finish_lists(const MatchBufs& b, int n_pairs, double ratio, in
     if (shmem > 150 * 1024) return hipErrorInvalidValue;
     sift_finish_kernel<<<n_pairs, 1024, dup, st>>>(b.recs, b.qlist, b.qmask, b.qcount, b.top2, b.slot1, b.slow_list,
                                                    b.slow_count, b.desc8, b.norm, b.dense_idx, ratio, distinct, min_count,
-                                                   b.counts, b.keep, b.unsettled);
+                                                   b.counts, b.keep, b.unsettled, n_pairs, b.offsets,
+                                                   b.scratch + SCRATCH_FINISH);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (ev_main && (e = hipEventRecord(ev_main, st)) != hipSuccess) return e;
-    scan_offsets_kernel<<<1, 1024, 0, st>>>(b.counts, n_pairs, b.offsets);
     assemble_lists_kernel<<<n_pairs, 1024, shmem, st>>>(b.recs, b.qlist, b.qcount, b.top2, b.dense_idx, b.dense_dist, distinct,
                                                         b.counts, b.offsets, b.out);
     return hipGetLastError();

@@ -129,7 +129,17 @@ struct sfmx_matcher {
     int64_t total_rows = 0;
     int max_rows = 0;
     bool any_nonintegral = false;
-    DevBuf raw, desc8, normv, keyc, keyc2, f32, flags, imgs_d;
+    DevBuf raw, desc8, normv, keyc, keyc2, f32, flags;
+    // One allocation, PrepImg[n] | ImgDev[n], so that set_images_device uploads both tables with one copy
+    DevBuf tabs;
+    DevView prep_tab, imgs_d;        // batched SIFT prep: one PrepImg per image; the kernels' image table
+    // Last-arriver tickets and the prepare kernel's partial maxima (match_common.hpp SCRATCH_*).  The kernels
+    // leave the tickets, and the prepare kernel the integrality flags, at zero.  scratch_clean says that they are:
+    // set_images and run clear it on entry and set it on success, so after an error return (a failed launch, a
+    // stream error, a call stopped half-way) the next call zeroes flags and scratch with one explicit fill each.
+    DevBuf scratch;
+    bool scratch_clean = false;
+    int64_t flags_split = 0;         // n_flags of the last set_images: flags[n_flags] | imax[2 n_flags]
     // FP6 screen (sift_fp6.hpp): packed e2m3 rows, f32 C-operand keys, (|u - 32|^2, |e|^2) per row; the
     // per-image maxima of |e|^2 and |u - 32|^2 live behind the integrality flags (imax: one fill for both)
     DevBuf desc6, keyf, ne;
@@ -147,9 +157,8 @@ struct sfmx_matcher {
     DevBuf porder, work2, work2_n;   // pair order (by train image) and the compacted pass-2 work list
     DevBuf recs;                     // list path: one flat PairRec per pair, in porder order
     DevView unsettled;               // int32: pass-1 forwarded queries pass 2 never wrote (must stay 0)
-    DevBuf prep_tab;                 // batched SIFT prep: one PrepImg per image
     PinnedBuf stage_prep, stage_run, stage_imgs, stage_flags; // pinned staging of the small uploads / flag readback
-    int32_t* hflags = nullptr;   // host-coherent mapped: integrality flags [hflags_cap] + sequence word (publish_flags_kernel)
+    int32_t* hflags = nullptr;   // host-coherent mapped: integrality flags [hflags_cap] + sequence word (prep_l2_batch_kernel's last workgroup)
     int hflags_cap = 0;
     unsigned flag_seq = 0;
     // Run plan cache: the device pair/work lists of the last run stay valid while the
@@ -339,6 +348,16 @@ int launch_route_diag(sfmx_matcher* m, const MatchRoute& route, const MatchBufs&
 }
 #endif
 
+// The tickets' buffer, at least `words` long; zeroed whole when it is allocated or grown, and when the last call
+// may have left a ticket behind (dirty: sfmx_matcher::scratch_clean was false).
+int ensure_scratch(sfmx_matcher* m, int64_t words, bool dirty, hipStream_t st) {
+    const size_t bytes = sizeof(int32_t) * (size_t)align_up(words, 64);
+    const bool grown = bytes > m->scratch.cap;
+    if (int rc = m->scratch.ensure(bytes)) return rc;
+    if (grown || dirty) HIPCHK(hipMemsetAsync(m->scratch.p, 0, m->scratch.cap, st));
+    return SFMX_OK;
+}
+
 int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hipStream_t st, bool device_src) {
     if (m) m->flags_pending = m->run_spec = false;   // (a pending check of earlier images is moot now)
     if (!m || (n > 0 && !imgs) || n < 0) return fail(SFMX_EINVAL, "null matcher/images");
@@ -358,6 +377,8 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
     MatchRoute route;   // ORB: the row layout follows the route; run_impl checks its own route against it
     if (int rc_ = resolve_route(norm, route)) return rc_;
     DeviceGuard g(m->device);
+    const bool dirty = !m->scratch_clean;   // (see scratch_clean: every return but the last leaves it false)
+    m->scratch_clean = false;
     m->norm = norm;
     m->orb_fp4 = norm == SFMX_NORM_HAMMING && route.orb != MatchRoute::ORB_VALU;
     m->n_imgs = n;
@@ -383,9 +404,15 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
     int rc;
     if ((rc = m->desc8.ensure((size_t)row * row_bytes))) return rc;
     const int64_t n_flags = align_up(std::max(n, 1), 64);   // flags[n_flags] | imax[2 n_flags]
+    // (a new allocation, or another split of it: imax words of the last call where this call's flags lie)
+    const bool relayout = n_flags != m->flags_split;   // (the same for the tickets and partial maxima of `scratch`)
+    const bool flags_grown = sizeof(int32_t) * 3 * n_flags > m->flags.cap || relayout;
     if ((rc = m->flags.ensure(sizeof(int32_t) * 3 * n_flags))) return rc;
+    m->flags_split = n_flags;
     m->imax.p = m->flags.as<int32_t>() + n_flags;
-    if ((rc = m->imgs_d.ensure(sizeof(ImgDev) * std::max(n, 1)))) return rc;
+    if ((rc = m->tabs.ensure((sizeof(PrepImg) + sizeof(ImgDev)) * std::max(n, 1)))) return rc;
+    m->prep_tab.p = m->tabs.p;
+    m->imgs_d.p = m->tabs.as<PrepImg>() + n;
     if (norm == SFMX_NORM_L2 && (rc = m->normv.ensure((size_t)row * 4))) return rc;
     if ((norm == SFMX_NORM_L2 || m->orb_fp4) && (rc = m->keyc.ensure((size_t)row * 4))) return rc;
     if (norm == SFMX_NORM_L2 && (rc = m->keyc2.ensure((size_t)row * 4))) return rc;
@@ -395,7 +422,10 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
         if ((rc = m->ne.ensure((size_t)row * sizeof(int2)))) return rc;
     }
     if (!device_src && (rc = m->raw.ensure((size_t)raw_bytes))) return rc;
-    HIPCHK(hipMemsetAsync(m->flags.p, 0, sizeof(int32_t) * 3 * n_flags, st));   // whole 256-B units: one dispatch
+    // L2: the prepare kernel leaves the flags at zero and stores every imax word it owns, so the fill is for a new
+    // allocation or a call that failed half-way.  Hamming: the fill of every call, as before (nothing reads it).
+    if (norm != SFMX_NORM_L2 || flags_grown || dirty)
+        HIPCHK(hipMemsetAsync(m->flags.p, 0, sizeof(int32_t) * 3 * n_flags, st));   // whole 256-B units: one dispatch
     std::vector<const void*> src(n);
     for (int i = 0; i < n; ++i) {
         const int64_t esz = norm == SFMX_NORM_L2 ? 4 : 1;
@@ -406,9 +436,10 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
             if (bytes) HIPCHK(hipMemcpyAsync((void*)src[i], imgs[i].data, bytes, hipMemcpyHostToDevice, st));
         }
     }
+    unsigned* hseq = nullptr;
+    unsigned want = 0;
     if (norm == SFMX_NORM_L2 && n > 0) {      // one launch for every image
-        if ((rc = m->stage_prep.ensure(sizeof(PrepImg) * n))) return rc;
-        if ((rc = m->prep_tab.ensure(sizeof(PrepImg) * n))) return rc;
+        if ((rc = m->stage_prep.ensure((sizeof(PrepImg) + sizeof(ImgDev)) * n))) return rc;
         PrepImg* tab = m->stage_prep.as<PrepImg>();
         int max_pad = 0;
         for (int i = 0; i < n; ++i) {
@@ -416,11 +447,29 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
             tab[i] = PrepImg{(const float*)src[i], d.rows, imgs[i].cols, d.rows_pad, 0, d.row0};
             max_pad = std::max(max_pad, d.rows_pad);
         }
-        HIPCHK(hipMemcpyAsync(m->prep_tab.p, tab, sizeof(PrepImg) * n, hipMemcpyHostToDevice, st));
+        // Device sources: every image counts as integral until the flags say otherwise (flags_pending), so the
+        // image table depends on nothing the kernel finds and goes up with the prepare table, in one copy.
+        if (device_src) std::memcpy(tab + n, m->imgs.data(), sizeof(ImgDev) * n);
+        HIPCHK(hipMemcpyAsync(m->tabs.p, tab, (sizeof(PrepImg) + (device_src ? sizeof(ImgDev) : 0)) * n, hipMemcpyHostToDevice, st));
         if ((rc = m->stage_prep.copied(st))) return rc;
+        if ((rc = ensure_scratch(m, scratch_words(n_flags, n, prep_l2_grid_x(max_pad)), dirty || relayout, st))) return rc;
+        if (n > m->hflags_cap) {
+            if (m->hflags) (void)hipHostFree(m->hflags);
+            m->hflags = nullptr;
+            m->hflags_cap = 0;
+            if (hipHostMalloc(reinterpret_cast<void**>(&m->hflags), sizeof(int32_t) * (n + 4),
+                              hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
+                return fail(SFMX_ENOMEM, "hipHostMalloc (integrality flags)");
+            m->hflags_cap = n;
+            m->hflags[n] = 0;
+        }
+        hseq = reinterpret_cast<unsigned*>(m->hflags + m->hflags_cap);
+        want = ++m->flag_seq;
+        // the kernel's last workgroup publishes the flags to hflags and release-stores `want` to the sequence word
         HIPCHK(launch_prep_l2_batch(m->prep_tab.as<PrepImg>(), n, max_pad, m->desc8.as<int8_t>(), m->normv.as<int32_t>(),
                                     m->keyc.as<int32_t>(), m->keyc2.as<int32_t>(), m->flags.as<int32_t>(),
-                                    m->desc6.as<uint32_t>(), m->keyf.as<float>(), m->ne.as<int2>(), m->imax.as<int32_t>(), st));
+                                    m->desc6.as<uint32_t>(), m->keyf.as<float>(), m->ne.as<int2>(), m->imax.as<int32_t>(),
+                                    m->scratch.as<int32_t>(), (int)n_flags, FlagHandoff{m->hflags, hseq, want}, st));
     }
     for (int i = 0; i < n && norm != SFMX_NORM_L2; ++i) {
         const ImgDev& d = m->imgs[i];
@@ -436,19 +485,6 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
     }
     m->any_nonintegral = false;
     if (norm == SFMX_NORM_L2 && n > 0) {
-        if (n > m->hflags_cap) {
-            if (m->hflags) (void)hipHostFree(m->hflags);
-            m->hflags = nullptr;
-            m->hflags_cap = 0;
-            if (hipHostMalloc(reinterpret_cast<void**>(&m->hflags), sizeof(int32_t) * (n + 4),
-                              hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-                return fail(SFMX_ENOMEM, "hipHostMalloc (integrality flags)");
-            m->hflags_cap = n;
-            m->hflags[n] = 0;
-        }
-        unsigned* hseq = reinterpret_cast<unsigned*>(m->hflags + m->hflags_cap);
-        const unsigned want = ++m->flag_seq;
-        HIPCHK(launch_publish_flags(m->flags.as<int32_t>(), n, m->hflags, hseq, want, st));
         if (device_src) {   // (see flags_pending) every image integral until the flags say otherwise
             m->flags_pending = true;
             m->flags_want = want;
@@ -484,13 +520,14 @@ int set_images_impl(sfmx_matcher* m, const sfmx_desc* imgs, int n, int norm, hip
             }
         }
     }
-    if (n > 0) {
+    if (n > 0 && !(norm == SFMX_NORM_L2 && device_src)) {   // (L2 device sources: went up with the prepare table)
         if ((rc = m->stage_imgs.ensure(sizeof(ImgDev) * n))) return rc;
         std::memcpy(m->stage_imgs.p, m->imgs.data(), sizeof(ImgDev) * n);
         HIPCHK(hipMemcpyAsync(m->imgs_d.p, m->stage_imgs.p, sizeof(ImgDev) * n, hipMemcpyHostToDevice, st));
         if ((rc = m->stage_imgs.copied(st))) return rc;
     }
     if (!device_src) HIPCHK(hipStreamSynchronize(st));   // host buffers may be released by the caller
+    m->scratch_clean = true;
     return SFMX_OK;
 }
 
@@ -615,8 +652,15 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
     m->unsettled.p = m->qcount.as<int32_t>() + n_pairs + 9;
     // the run's only fill; whole 256-B units, which the runtime clears in one dispatch (no unaligned tail)
     HIPCHK(hipMemsetAsync(m->qcount.p, 0, sizeof(int32_t) * align_up(arena_words(n_pairs), 64), st));
+    const bool dirty = !m->scratch_clean;   // (see scratch_clean: every return but the last leaves it false)
+    m->scratch_clean = false;
+    if ((rc = ensure_scratch(m, SCRATCH_IMG, dirty, st))) return rc;
     HIPCHK(hipEventRecord(m->ev[0], st));
-    HIPCHK(hipEventRecord(m->ev[3], st));   // re-recorded after pass 1 by the two-pass launchers
+    // ev[3]: the product launchers record it behind the screen whenever there is a work item, and nothing reads it
+    // in between (timing, timing_history and pass_timing wait for ev[2] first).  Every other route, and a run
+    // without work, keeps the record here (the two-pass launchers of the diagnostic routes record it again).
+    const bool product = route.batches == 1 && (sift ? route.sift_product() : route.orb_product());
+    if (!(product && n_work > 0)) HIPCHK(hipEventRecord(m->ev[3], st));
     // Pairs with an empty left image have no work item; pairs with an empty
     // right image are handled in-kernel (every query: no neighbour).
     MatchBufs B{};
@@ -651,6 +695,7 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
     B.keep = m->keep.as<int32_t>();
     B.offsets = m->offsets.as<int64_t>();
     B.out = m->out.as<DMatchDev>();
+    B.scratch = m->scratch.as<int32_t>();
 #ifdef SFMX_DIAG
     if ((rc = launch_route_diag(m, route, B, (int)n_work, n_pairs, ratio, st))) return rc;
 #else
@@ -679,6 +724,7 @@ int run_impl(sfmx_matcher* m, const int32_t* pairs, int n_pairs, double ratio, i
         m->last_distinct = distinct;
         m->last_min_count = min_count;
     }
+    m->scratch_clean = true;
     return SFMX_OK;
 }
 
@@ -825,7 +871,7 @@ int sfmx_matcher_destroy(sfmx_matcher* m) {
         m->stage_flags.release();
         if (m->hflags) (void)hipHostFree(m->hflags);
         m->hflags = nullptr;
-        DevBuf* bufs[] = {&m->raw, &m->desc8, &m->normv, &m->keyc, &m->keyc2, &m->desc6, &m->keyf, &m->ne, &m->qlist, &m->qcount, &m->porder, &m->work2, &m->work2_n, &m->f32, &m->flags, &m->imgs_d, &m->pairs_d, &m->prep_tab,
+        DevBuf* bufs[] = {&m->raw, &m->desc8, &m->normv, &m->keyc, &m->keyc2, &m->desc6, &m->keyf, &m->ne, &m->qlist, &m->qcount, &m->porder, &m->work2, &m->work2_n, &m->f32, &m->flags, &m->tabs, &m->pairs_d, &m->scratch,
                           &m->work_d, &m->work32_d, &m->dense_idx, &m->dense_dist, &m->slow_list,
                           &m->counts, &m->keep, &m->offsets, &m->out, &m->qmask, &m->top2, &m->recs};
         for (DevBuf* b : bufs) b->release();
@@ -856,7 +902,9 @@ int sfmx_matcher_run(sfmx_matcher* m, const int32_t* pairs, int32_t n_pairs, dou
 
 int sfmx_matcher_fetch(sfmx_matcher* m, sfmx_dmatch* out, int64_t cap, int64_t* required, int64_t* pair_offsets,
                        int32_t* keep, void* stream) {
-    return fetch_impl(m, out, cap, required, pair_offsets, keep, (hipStream_t)stream);
+    const int rc = fetch_impl(m, out, cap, required, pair_offsets, keep, (hipStream_t)stream);
+    if (m && (rc == SFMX_EDEVICE || rc == SFMX_EINTERNAL)) m->scratch_clean = false;   // a stream error: a kernel may have stopped half-way
+    return rc;
 }
 
 int sfmx_matcher_device_results(sfmx_matcher* m, const sfmx_dmatch** matches, const int64_t** pair_offsets,
@@ -881,7 +929,10 @@ int sfmx_matcher_stats(sfmx_matcher* m, int64_t* slow_queries, int64_t* fp32_pai
     int32_t sc = 0, unsettled = 0;
     HIPCHK(hipMemcpyAsync(&sc, m->slow_count.p, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(hipMemcpyAsync(&unsettled, m->unsettled.p, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    if (const hipError_t e = hipStreamSynchronize((hipStream_t)stream); e != hipSuccess) {
+        m->scratch_clean = false;   // a stream error: a kernel may have stopped half-way
+        return fail(SFMX_EDEVICE, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    }
     if (unsettled) return fail(SFMX_EINTERNAL, std::to_string(unsettled) + " forwarded queries were not settled by pass 2");
     if (slow_queries) *slow_queries = sc;
     if (fp32_pairs) *fp32_pairs = m->fp32_pairs;
