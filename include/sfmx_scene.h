@@ -146,18 +146,27 @@ int sfmx_ba_observations_from_origins(const int64_t* origin_offsets, int32_t n_p
  *   out_origin_shot/_xy    capacity: cloud records + new records
  *   out_n_points, out_n_origins   host memory, always
  * The out_* arrays must not overlap the inputs (old records move within the CSR).
- * SFMX_EINVAL (found on the host before any launch): a NaN merge distance, offsets
- * that do not ascend from 0, an origin or pair shot outside [0, n_shots),
- * n_cloud + n_new beyond int32.  n_new == 0 copies the cloud through and, with host
- * inputs, touches no device.  A hash table that fills up: SFMX_EINTERNAL; more than
- * 2^31 links among the new elements, 2^30 records in a cloud or 2^29 matches:
- * SFMX_ECAPACITY (merge the elements in several calls).
+ * SFMX_EINVAL: a NaN merge distance, offsets that do not ascend from 0, an origin
+ * or pair shot outside [0, n_shots), n_cloud + n_new beyond int32.  With host inputs
+ * all of these are found on the host before any launch; with device inputs the two
+ * origin offset arrays and the origin shots are checked by a kernel, the error is
+ * returned after it and the outputs are unspecified.  n_new == 0 copies the cloud
+ * through and, with host inputs, touches no device.  A hash table that fills up:
+ * SFMX_EINTERNAL; more than 2^31 links among the new elements, 2^30 records in a
+ * cloud or 2^29 matches: SFMX_ECAPACITY (merge the elements in several calls).
  * inputs_on_device = 1: keypoints[i], matches, pair_offsets, both clouds' arrays
  * and the out_* arrays except the two counts are device pointers on `device`;
- * 0: host memory.  In device mode the call stages through host memory: the
- * per-element summaries and link lists of the sequential resolution, and both
- * clouds' coordinates and origin records, which that resolution and the record
- * dedupe read. */
+ * 0: host memory.
+ * The merge-or-append decisions and the record dedupe run on the device: the
+ * decisions in rounds (an element is decided in the first round after all the
+ * earlier elements it is linked to), one word read by the host per round.  In
+ * device mode the host reads pair_offsets, the last entry of both origin offset
+ * arrays and a few result words, and uploads its per-shot and per-pair tables:
+ * nothing of either cloud, of the matches or of the links crosses.  A call that
+ * still has undecided elements after the cap of
+ * sfmx_merge_pointcloud_set_max_rounds finishes on the host instead, with the same
+ * result: it then stages the per-element summaries, the link lists and, in device
+ * mode, both clouds' coordinates and origin records. */
 int sfmx_merge_pointcloud_3d2d(const sfmx_point2f* const* keypoints, const int32_t* n_keypoints, int32_t n_shots,
                                const int32_t* pairs, int32_t n_pairs, const sfmx_dmatch* matches,
                                const int64_t* pair_offsets, const double* cloud_xyz, int32_t n_cloud,
@@ -171,9 +180,22 @@ int sfmx_merge_pointcloud_3d2d(const sfmx_point2f* const* keypoints, const int32
                                int64_t* out_n_origins);
 
 /* Device time (ms) of the last sfmx_merge_pointcloud_3d2d call on this thread
- * (table build + probe, link fill and scatter kernels, HIP events on its stream;
- * the host resolution between them is not in it); 0 for n_new == 0, -1 before any call. */
+ * (validation, table build + probe, link fill, scans, resolve rounds, dedupe and
+ * scatter kernels, HIP events on its stream; the copies and, after a fallback, the
+ * host resolution between them are not in it); 0 for n_new == 0, -1 before any call. */
 float sfmx_merge_pointcloud_last_kernel_ms(void);
+
+/* The cap on the resolve rounds of this thread's later sfmx_merge_pointcloud_3d2d
+ * calls: 0 the library default, > 0 that cap, < 0 no device
+ * resolution: the host resolution always.  The results do not depend on it. */
+int sfmx_merge_pointcloud_set_max_rounds(int32_t max_rounds);
+
+/* About the last sfmx_merge_pointcloud_3d2d call on this thread (any pointer may be
+ * NULL; zeros before any call): the resolve rounds it launched, 1 if the host
+ * resolution decided its result (the cap was reached, or a negative setting), and
+ * every byte it copied host to device or device to host, the pinned table upload
+ * included. */
+int sfmx_merge_pointcloud_last_path(int32_t* rounds, int32_t* host_fallback, int64_t* host_bytes);
 
 /* Counts of the last sfmx_merge_pointcloud_3d2d call on this thread (any pointer
  * may be NULL): merges whose winner qualifies through a record it held when the

@@ -40,7 +40,8 @@ void first_record_of_pair_kernel(int64_t n_rec, const int32_t* __restrict__ foun
 // between the rows: the keypoints go up once, the packed match lists, the cloud (coordinates and origin CSR) and what
 // one row hands the next stay there, and every row is called with inputs_on_device = 1.  A list that shrinks to its
 // inliers is repacked on the device.  The host sees the pair offsets, the counts, statuses and poses, and for the
-// adjustment the cloud (sfmx_ba_solve takes host arrays); the merge stages its own resolution (sfmx_scene.h).
+// adjustment the cloud (sfmx_ba_solve takes host arrays); the merge reads the pair offsets and a few words and stages
+// the cloud only when its resolution falls back to the host (sfmx_scene.h).
 struct Rows {
     const sfmx_point2f* const* kp;
     const int32_t* nkp;
@@ -262,7 +263,11 @@ struct Rows {
         }
         if (rc < 0) return rc;
         device_ms(SFMX_SFM_ROW_MERGE, sfmx_merge_pointcloud_last_kernel_ms());
-        tm.handoff_bytes[SFMX_SFM_ROW_MERGE] += 4 + 8;
+        {   // every byte the call copied between host and device, the two counts included
+            int64_t bytes = 0;
+            (void)sfmx_merge_pointcloud_last_path(nullptr, nullptr, &bytes);
+            tm.handoff_bytes[SFMX_SFM_ROW_MERGE] += bytes;
+        }
         if (k < n_points || k > n_points + n_new || r < n_rec || r > n_rec + 2 * n_new) {
             set_last_error("merge: cloud size self check failed");
             return SFMX_EINTERNAL;

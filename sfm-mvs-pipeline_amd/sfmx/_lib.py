@@ -241,6 +241,8 @@ PROTOTYPES = {
                                              _vp, _vp, _vp, _vp, _vp, _vp, _i32p, _i64p]),
     "sfmx_merge_pointcloud_last_kernel_ms": (C.c_float, []),
     "sfmx_merge_pointcloud_last_stats": (C.c_int, [_i64p, _i64p, _i64p]),
+    "sfmx_merge_pointcloud_set_max_rounds": (C.c_int, [C.c_int32]),
+    "sfmx_merge_pointcloud_last_path": (C.c_int, [_i32p, _i32p, _i64p]),
     "sfmx_cloud_neighbor_distances": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "sfmx_cloud_last_stats": (C.c_int, [_P(C.c_float), _i64p, _i64p]),
     "sfmx_cloud_statistics": (C.c_int, [_vp, C.c_int64, C.c_int64, _P(sfmx_cloud_stats)]),

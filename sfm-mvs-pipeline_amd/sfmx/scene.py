@@ -257,3 +257,17 @@ def merge_last_stats() -> dict:
     a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     check(lib.sfmx_merge_pointcloud_last_stats(C.byref(a), C.byref(b), C.byref(c)), "sfmx_merge_pointcloud_last_stats")
     return dict(merged_static=int(a.value), merged_dynamic=int(b.value), links=int(c.value))
+
+
+def merge_set_max_rounds(max_rounds: int) -> None:
+    """The cap on the device resolution's rounds for this thread's merge calls: 0 the library default, > 0 that
+    cap, < 0 always the host resolution.  A call that reaches the cap finishes on the host, with the same result."""
+    check(lib.sfmx_merge_pointcloud_set_max_rounds(int(max_rounds)), "sfmx_merge_pointcloud_set_max_rounds")
+
+
+def merge_last_path() -> dict:
+    """How the last merge call on this thread ran: resolve rounds launched, whether the host resolution decided
+    the result, and every byte the call copied between host and device."""
+    a, b, c = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    check(lib.sfmx_merge_pointcloud_last_path(C.byref(a), C.byref(b), C.byref(c)), "sfmx_merge_pointcloud_last_path")
+    return dict(rounds=int(a.value), host_fallback=int(b.value), host_bytes=int(c.value))

@@ -7,7 +7,9 @@ on the device.  The pairs are triangulated on the device; the cloud is the merge
 `--cloud-pairs` pairs' points into an empty cloud (not timed), and the timed call merges the remaining
 pairs' points into that cloud.  Prints one JSON line: kernel time from the call's HIP events
 (sfmx_merge_pointcloud_last_kernel_ms, median of `--steps` calls after `--warmup`), wall time of the call
-(it includes the host resolution and the staging copies), elements/s on both, the merges into points that
+(it includes the per-round word reads and, after a fallback, the host resolution and the staging copies), the
+resolve rounds, whether the call fell back to the host and the bytes it copied between host and device
+(sfmx_merge_pointcloud_last_path), elements/s on both, the merges into points that
 qualify through call-start records (static) and only through what the call itself added (dynamic), and the bytes the kernels must
 touch (inputs read, tables written and probed once, outputs written) over the kernel time and the HBM peak.
 
@@ -39,6 +41,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--max-rounds", type=int, default=0,
+                    help="cap on the resolve rounds: 0 the library default, < 0 the host resolution always")
     a = ap.parse_args()
     import torch
     from sfmx import scene, triangulate
@@ -61,6 +65,7 @@ def main():
     empty = (torch.zeros((0, 3), dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
              torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros((0, 2), dtype=torch.float64, device=dev))
     D, F = a.point_merge_distance, a.feature_merge_distance
+    scene.merge_set_max_rounds(a.max_rounds)
     merge = lambda cloud, new: scene.merge_pointcloud_3d2d_device(kptr, nkp, pairs, dm.data_ptr(), do.data_ptr(), *cloud, *new, D, F)
     t0 = time.perf_counter()
     c = merge(empty, part(0, k0))
@@ -77,6 +82,7 @@ def main():
         wall.append((time.perf_counter() - t0) * 1e3)
         ms.append(scene.merge_last_kernel_ms())
     st = scene.merge_last_stats()
+    path = scene.merge_last_path()
     n_cloud, n_new = len(cloud[0]), len(new[0])
     rc, rn, ro = len(cloud[2]), len(new[2]), len(r["origin_shot"])
     kernel_ms, wall_ms = float(np.median(ms)), float(np.median(wall))
@@ -90,6 +96,9 @@ def main():
         "merged_static": st["merged_static"], "merged_dynamic": st["merged_dynamic"], "new_new_links": st["links"],
         "kernel_ms": round(kernel_ms, 4), "kernel_ms_min": round(float(np.min(ms)), 4),
         "kernel_ms_max": round(float(np.max(ms)), 4), "call_wall_ms": round(wall_ms, 3),
+        "call_wall_ms_min": round(float(np.min(wall)), 3), "call_wall_ms_max": round(float(np.max(wall)), 3),
+        "max_rounds": a.max_rounds, "rounds": path["rounds"], "host_fallback": path["host_fallback"],
+        "host_bytes": path["host_bytes"],
         "elements_per_s_kernel": round(n_new / (kernel_ms * 1e-3), 1), "elements_per_s_wall": round(n_new / (wall_ms * 1e-3), 1),
         "bytes_moved": moved, "io_gbs": round(moved / (kernel_ms * 1e-3) / 1e9, 2),
         "hbm_frac": round(moved / (kernel_ms * 1e-3) / (HBM_PEAK_GBS * 1e9), 5),

@@ -8,7 +8,8 @@
     it replaces, alternating, median of --steps after --warmup: kernel time (HIP events) and wall time of both.
 (b) --case loop: sfmx_sfm_triangulate end to end on a synthetic scene of --shots x --points (tests/sfm_cases.py
     geometry, every shot matched with its next --seq shots): wall ms per registered shot, split by row, and the
-    bytes of host arrays each row is handed.
+    bytes of host arrays each row is handed (the merge row's: every byte its calls copied between host and device),
+    and the rounds, host fallback and bytes of the loop's last merge call.
 
     python tools/sfm_bench.py --case count [--steps 10] [--warmup 2]
     python tools/sfm_bench.py --case loop [--shots 50] [--points 2000] [--seq 5] [--steps 3] [--warmup 1]
@@ -111,8 +112,9 @@ def case_count(a):
 
 def case_loop(a):
     import sfm_cases
-    from sfmx import ba, sfm
+    from sfmx import ba, scene, sfm
     sc = sfm_cases.build(a.shots, a.points, graph=("seq", a.seq), seed=31)
+    scene.merge_set_max_rounds(a.max_rounds)
     runs = []
     for i in range(a.warmup + a.steps):
         ba.release_cache()
@@ -122,6 +124,7 @@ def case_loop(a):
         w = (time.perf_counter() - t0) * 1e3
         if i >= a.warmup:
             runs.append((w, r))
+    path = scene.merge_last_path()   # the loop's last merge call: the one into the largest cloud
     w, r = sorted(runs, key=lambda x: x[0])[len(runs) // 2]
     reg = max(int(r["recovered"].sum()), 1)
     t = r["timing"]
@@ -133,6 +136,7 @@ def case_loop(a):
                       "last_termination_type": r["summary"]["last_termination_type"],
                       "wall_ms": round(w, 2), "wall_ms_per_registered_shot": round(w / reg, 3),
                       "outside_rows_ms": round(w - total_rows, 2),
+                      "merge_max_rounds": a.max_rounds, "merge_last_call": path,
                       "rows": {k: {"calls": v["calls"], "wall_ms": round(v["wall_ms"], 2), "device_ms": round(v["device_ms"], 2),
                                    "wall_ms_per_registered_shot": round(v["wall_ms"] / reg, 3),
                                    "share": round(v["wall_ms"] / w, 4), "handoff_bytes": v["handoff_bytes"]} for k, v in t.items()}}))
@@ -148,6 +152,8 @@ def main():
     ap.add_argument("--shots", type=int, default=50)
     ap.add_argument("--points", type=int, default=2000)
     ap.add_argument("--seq", type=int, default=5)
+    ap.add_argument("--max-rounds", type=int, default=0,
+                    help="loop case: cap on the merge's resolve rounds (0 the library default, < 0 the host resolution always)")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
